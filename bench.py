@@ -1,8 +1,12 @@
 #!/usr/bin/env python
 """bench.py — mapped Gbp/s of the seed→chain→align hot path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
-  (N > 1: launched by torch.distributed.run, one rank per GPU over RCCL; see the contract in the task statement)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  (N > 1: launched by torch.distributed.run, one rank per GPU over RCCL)
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (`value`, `ms_per_step` = wall time of the timed
+region / K, `roofline` and `host` from the same timed steps). `--dump-outputs DIR` writes what the last timed step returned
+(see dump_outputs). `--full` adds the legs that take runs of their own: `file_to_file`, `cpu_baseline` and `parity` below.
 
 Workload (BASELINE.json configs[1]): 15 kb ONT-profile reads (3 % sub, 3 % ins, 4 % del, 1 % of
 reads with one SV) against a 250 Mb synthetic reference (25 contigs x 10 Mb, 10 % repeat families incl. 171-bp
@@ -10,6 +14,8 @@ satellite arrays), `-W` list = canonical 15-mers above the 0.9998-distinct thres
 A STEP = one mini-batch of reads (--reads-per-step per rank; default 65 536 x 15 kb = 0.98 Gbase, the reference's own
 mini-batch size `-K 1G`, src/options.c:50) through the full path: sketch → seed → chain → ksw kernels with
 the host MCAS glue in between; reads shard across ranks (weak scaling: per-GPU work is fixed), no data-path collective.
+The reads are drawn READ_CHUNK at a time, each chunk from its own seed (config seed, rank, chunk), by one forked process per usable
+core: the same arguments give the same reads whatever the number of processes.
 The `-W` list is counted and the reference index is built by rank 0 ON ITS GPU (wm_write_repetitive_kmers_gpu, wm_index_build_gpu: one
 wavefront per contig sketches the reference) and broadcast with RCCL (torch.distributed "nccl") as flat arrays — outside the timed region.
 
@@ -19,18 +25,23 @@ are uploaded once and every alignment / sketch request refers to positions in th
 `host`: where the host time of the timed region went (per-read glue, batched calls, helpers, idle) against the usable cores.
 `roofline`: dominant kernel = ksw_dp (1 B of traceback per DP cell is > 99 % of the path's algorithmic bytes);
 achieved = DP cells of the timed steps ÷ the kernels' summed duration (HIP events on their streams).
-`cpu_baseline`: the REAL reference (oracle/_ref/winnowmap_ref, built from /root/reference) mapping ONE FULL STEP of the
+`file_to_file` (--full): reads.fa -> out.paf through wm_map_file on the first two mini-batches.
+`cpu_baseline` (--full): the REAL reference (oracle/_ref/winnowmap_ref, built by oracle/Makefile from the reference's sources) mapping ONE FULL STEP of the
 same reads against the same reference on this host, swept over thread counts; the BEST mapping-phase rate is reported.
-`parity`: the reference's PAF records for that step are diffed against ours for the same reads (every column and tag
+`parity` (--full): the reference's PAF records for that step are diffed against ours for the same reads (every column and tag
 except MAPQ / rl:i, see winnowmap_amd/parity.py); outside the timed region.
 `--config 3` switches to BASELINE config 3 (50 000 x 20 kb HiFi reads, map-pb); config 2 stays the default.
 `--gpus N` without a torch.distributed environment re-launches itself under torch.distributed.run with N ranks.
 """
 import argparse
+import ctypes as C
 import json
+import mmap
+import multiprocessing
 import os
 import re
 import resource
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -50,12 +61,19 @@ def log(*a):
     print("[bench]", *a, file=sys.stderr, flush=True)
 
 
-def make_workload(ref_mb, tmp, ctx=None):
-    """the synthetic reference and its -W list (counted on the device when a context is given, on the host otherwise: same file)"""
+def make_reference(ref_mb):
+    """the seeded synthetic reference of --ref-mb megabases (10 Mb contigs)"""
     n_contigs = max(1, int(round(ref_mb / 10.0)))
-    clen = int(ref_mb * 1e6 / n_contigs)
+    return synth.make_reference(n_contigs, int(ref_mb * 1e6 / n_contigs), 3, repeat_frac=0.10)
+
+
+def make_workload(ref_mb, tmp, ctx=None, ref=None):
+    """the synthetic reference (unless given) and its -W list (counted on the device when a context is given, on the host otherwise: same file)"""
     t0 = time.time()
-    ref = synth.make_reference(n_contigs, clen, 3, repeat_frac=0.10)
+    given = ref is not None
+    if not given:
+        ref = make_reference(ref_mb)
+    n_contigs, clen = len(ref), len(ref[0])
     fa = os.path.join(tmp, "ref.fa")
     synth.write_fasta(fa, ref, prefix="ctg")
     kf = os.path.join(tmp, "repetitive_k15.txt")
@@ -64,7 +82,7 @@ def make_workload(ref_mb, tmp, ctx=None):
         n_k, st = gpu.write_repetitive_kmers_gpu(ctx, fa, 15, kf)
     else:
         n_k = gpu.write_repetitive_kmers(fa, 15, kf)
-    log("reference %d x %d bp (%.1fs), -W list %d k-mers (%.1fs on the %s)" % (n_contigs, clen, t1 - t0, n_k, time.time() - t1, "device" if ctx is not None else "host"))
+    log("reference %d x %d bp (%.1fs%s), -W list %d k-mers (%.1fs on the %s)" % (n_contigs, clen, t1 - t0, ", FASTA only" if given else "", n_k, time.time() - t1, "device" if ctx is not None else "host"))
     return ref, fa, kf
 
 
@@ -76,6 +94,74 @@ CONFIGS = {
     # (~1.2 x 10^8 minimizers, a 2^28-slot table) no longer sits in L2, which is what changes for the seed stage (src/index.c:88-105)
     4: {"preset": "map-ont", "profile": "ont", "read_len": 15000, "reads_per_step": 65536, "sv_frac": 0.01, "seed": 4, "label": "ONT-profile", "ref_mb": 3000.0},
 }
+
+
+READ_CHUNK = 1024      # reads drawn from one seed: the reads depend on (seed, chunk), not on how many processes draw them
+_GEN = None            # (reference, reads, read length, seed, config, output buffer) for the forked generator processes
+
+
+def _gen_chunks(chunks):
+    """reads [c * READ_CHUNK, (c + 1) * READ_CHUNK) of the batch for each chunk c, from seed (seed, c), as ASCII into the shared buffer"""
+    ref, n, read_len, seed, cfg, buf = _GEN
+    a = np.frombuffer(buf, np.uint8)
+    for c in chunks:
+        lo = c * READ_CHUNK
+        reads, _ = synth.make_reads(ref, min(READ_CHUNK, n - lo), read_len, [seed, c], profile=cfg["profile"], sv_frac=cfg["sv_frac"])
+        for j, r in enumerate(reads):
+            a[(lo + j) * read_len:(lo + j + 1) * read_len] = np.frombuffer(synth.codes_to_ascii(r), np.uint8)
+
+
+def make_read_blob(ref, n, read_len, seed, cfg, n_procs):
+    """n reads of exactly read_len bases, back to back in one uint8 array, drawn by n_procs forked processes into a shared buffer (call it
+    before this process opens the GPU: the children only run numpy) and copied into this process's own memory, touched before any clock starts"""
+    global _GEN
+    buf = mmap.mmap(-1, n * read_len)
+    n_chunks = (n + READ_CHUNK - 1) // READ_CHUNK
+    n_procs = max(1, min(n_procs, n_chunks))
+    _GEN = (ref, n, read_len, seed, cfg, buf)
+    try:
+        if n_procs == 1:
+            _gen_chunks(range(n_chunks))
+        else:
+            procs = [multiprocessing.get_context("fork").Process(target=_gen_chunks, args=(range(k, n_chunks, n_procs),)) for k in range(n_procs)]
+            for p in procs:
+                p.start()
+            for p in procs:
+                p.join()
+            if any(p.exitcode != 0 for p in procs):
+                raise RuntimeError("read generator processes failed: exit codes %s" % [p.exitcode for p in procs])
+    finally:
+        _GEN = None
+    blob = np.frombuffer(buf, np.uint8).copy()
+    buf.close()
+    return blob
+
+
+def marshal_blob(names, blob, lo, n, read_len):
+    """Mapper.marshal() of reads lo .. lo + n - 1 of the uint8 array without copying them: the sequence pointers point into the array"""
+    sq = (C.c_char_p * n)()
+    addr = np.uint64(blob.ctypes.data) + np.arange(lo, lo + n, dtype=np.uint64) * np.uint64(read_len)
+    C.memmove(sq, addr.ctypes.data, addr.nbytes)
+    nm = (C.c_char_p * n)(*names)
+    return n, nm, sq, np.full(n, read_len, np.int32), (names, blob)
+
+
+DUMP_LIMITS = {"text_bytes": 1024, "first": 15_000_000, "hits": 48_000_000}      # bytes per array incl. the row indices of a sample: < 64 MB in all
+
+
+def dump_outputs(out_dir, tlen, hits, first):
+    """--dump-outputs: what the timed path's caller received for the last timed step (Mapper.map(..., copy_text=False): the length of the
+    PAF text, the hit table [n_hits, 16], each read's first hit [n + 1]) as float64 (exact for these integers). An array above its limit is
+    replaced by a fixed, seeded sample of its rows, whose indices are written beside it as <name>_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"text_bytes": np.array([tlen], np.float64), "first": first.astype(np.float64), "hits": hits.astype(np.float64)}
+    for name, a in arrays.items():
+        if a.nbytes > DUMP_LIMITS[name]:
+            rows = np.sort(np.random.default_rng(0).choice(len(a), DUMP_LIMITS[name] // (a.nbytes // len(a) + 8), replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("outputs of the last timed step written to %s (%d hits)" % (out_dir, len(hits)))
 
 
 def cpu_model():
@@ -296,7 +382,12 @@ def main():
     ap.add_argument("--read-len", type=int, default=0)
     ap.add_argument("--threads", type=int, default=int(os.environ.get("WM_BENCH_THREADS", 0)))
     ap.add_argument("--cpu-sample", type=int, default=int(os.environ.get("WM_BENCH_CPU_SAMPLE", -1)),
-                    help="reads of the CPU baseline / parity leg: -1 = one full step, 0 = skip the leg")
+                    help="reads of the CPU baseline / parity leg of --full: -1 = one full step, 0 = skip the leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also the legs that take runs of their own: file to file (wm_map_file), the CPU baseline "
+                         "(the reference binary on this host's cores) and the parity diff against it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (text length, hits, first hit per read) to DIR/<name>.npy as float64")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
     args.reads_per_step = args.reads_per_step or cfg["reads_per_step"]
@@ -316,15 +407,6 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", 0))
     if world != args.gpus:
         sys.exit("bench.py: --gpus %d but WORLD_SIZE=%d (launch with torch.distributed.run --nproc-per-node %d, or plainly and let bench.py launch the ranks)" % (args.gpus, world, args.gpus))
-    import torch
-    dist = None
-    if world > 1 or os.environ.get("WM_BENCH_FORCE_DIST"):     # (the env switch lets a 1-GPU box exercise the RCCL code path)
-        import torch.distributed as dist
-        if torch.cuda.device_count() <= local:
-            sys.exit("bench.py: rank %d has no GPU %d (%d visible)" % (rank, local, torch.cuda.device_count()))
-        torch.cuda.set_device(local)
-        dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-        assert dist.get_world_size() == args.gpus and dist.get_backend() == "nccl"
     n_cores = wmdist.available_cores()       # hardware threads, affinity and the container CPU quota
     # host threads per rank: the ranks of one node share its cores — divide them explicitly
     n_threads = args.threads or wmdist.host_threads_per_rank(n_cores, world)
@@ -333,30 +415,11 @@ def main():
             "so this node's host side, not its GPUs, bounds the scaling curve" % (n_cores, world, n_threads, "35"))
     tmp = tempfile.mkdtemp(prefix="wmbench_")
 
-    # ---- reference + index: rank 0 builds, RCCL broadcasts the flat arrays ----
-    t0 = time.time()
-    # device contexts (own streams + arena each: that many batched calls are on the device at once) share the 288 GB of HBM
-    n_ctx = int(os.environ.setdefault("WM_CONTEXTS", "6"))
-    arena = int(float(os.environ.get("WM_BENCH_ARENA_GB", min(48.0, 216.0 / n_ctx))) * (1 << 30))
-    ctx = gpu.Context(local, arena)
-    if rank == 0:
-        ref, fa, kf = make_workload(args.ref_mb, tmp, ctx)
-        t_i = time.time()
-        idx, ist = gpu.Index.build_on_device(ctx, fa, kf, k=15, w=50, n_threads=min(64, n_cores))      # map-ont and map-pb: k=15, w=50 (src/options.c:94-103)
-        log("index: %d minimizers, built in %.1fs (reference sketched on the device in %.2fs)" % (idx.n_minimizers, time.time() - t_i, ist["device_sketch_s"]))
-    if dist is not None:
-        dev = torch.device("cuda", local)
-        idx, uploaded = wmdist.broadcast_index(idx if rank == 0 else None, rank, dist, dev, ctx)      # RCCL over xGMI, one broadcast per flat array, received straight into the context
-        # every rank regenerates the (seeded) reference only to draw its reads from it
-        if rank != 0:
-            n_contigs = max(1, int(round(args.ref_mb / 10.0)))
-            ref = synth.make_reference(n_contigs, int(args.ref_mb * 1e6 / n_contigs), 3, repeat_frac=0.10)
-    if dist is None or not uploaded:
-        idx.upload(ctx)
-    os.environ.setdefault("WM_READ_SLABS", str(max(1, min(4, int(os.environ.get("WM_BENCH_SLOTS", 2))))))      # resident read slabs = mini-batches in flight (below)
-    mapper = gpu.Mapper(ctx, idx, cfg["preset"], gpu.MM_F_CIGAR | gpu.MM_F_OUT_CG)
-    if n_threads > 1:
-        mapper.set_threads(n_threads, arena)
+    # ---- host inputs first, before this process opens the GPU (the reads are drawn by forked processes): the seeded reference, of which
+    # rank 0 builds the index and from which every rank draws its reads ----
+    t1 = time.time()
+    ref = make_reference(args.ref_mb)
+    log("reference generated (%.1fs)" % (time.time() - t1))
 
     # ---- reads: a fresh batch per step, generated before the clock starts ----
     t1 = time.time()
@@ -368,27 +431,57 @@ def main():
     # the warm-up; the JSON line says how many timed steps ran on batches first seen inside the timed region — all batches have the same shape, so
     # what a first sight costs is the growth of pinned pools / result buffers to this batch's hit count)
     n_distinct = min(n_steps, int(os.environ.get("WM_BENCH_DISTINCT_BATCHES", 4)))
+    n_reads, rps, rlen = n_distinct * args.reads_per_step, args.reads_per_step, args.read_len
     # WM_BENCH_CACHE=<dir>: A/B runs of one GPU call share the generated reads (same seeds = same reads; only the generation time is saved)
     cache = os.environ.get("WM_BENCH_CACHE")
-    cpath = os.path.join(cache, "reads_c%d_r%d_n%d_l%d_m%d.npz" % (args.config, rank, n_distinct * args.reads_per_step, args.read_len, int(args.ref_mb))) if cache else None
+    cpath = os.path.join(cache, "reads_c%d_r%d_n%d_l%d_m%d_k%d.npy" % (args.config, rank, n_reads, rlen, int(args.ref_mb), READ_CHUNK)) if cache else None
     if cpath and os.path.exists(cpath):
-        z = np.load(cpath)
-        blob, ends = z["blob"].tobytes(), z["ends"]
-        seqs = [blob[(ends[i - 1] if i else 0):ends[i]] for i in range(len(ends))]
-        del blob
+        blob = np.load(cpath)
     else:
-        reads, _ = synth.make_reads(ref, n_distinct * args.reads_per_step, args.read_len, cfg["seed"] + 1000 * rank, profile=cfg["profile"], sv_frac=cfg["sv_frac"])
-        seqs = [synth.codes_to_ascii(r) for r in reads]
-        del reads
+        # one seed per READ_CHUNK reads, drawn by one process per usable core of this rank
+        blob = make_read_blob(ref, n_reads, rlen, cfg["seed"] + 1000 * rank, cfg, max(1, n_cores // world))
         if cpath:
             os.makedirs(cache, exist_ok=True)
-            np.savez(cpath, blob=np.frombuffer(b"".join(seqs), np.uint8), ends=np.cumsum([len(x) for x in seqs]))
-    names = [("r%d_%d" % (rank, i)).encode() for i in range(len(seqs))]
-    distinct = [(names[i * args.reads_per_step:(i + 1) * args.reads_per_step], seqs[i * args.reads_per_step:(i + 1) * args.reads_per_step]) for i in range(n_distinct)]
-    marshalled = [gpu.Mapper.marshal(*d) for d in distinct]       # the C argument arrays of wm_map_reads, built once (not the mapper's work)
-    batches = [distinct[i % n_distinct] for i in range(n_steps)]
+            np.save(cpath, blob)
+    names = [("r%d_%d" % (rank, i)).encode() for i in range(n_reads)]
+    # the C argument arrays of wm_map_reads, built once (not the mapper's work); the sequences stay in the array
+    marshalled = [marshal_blob(names[b * rps:(b + 1) * rps], blob, b * rps, rps, rlen) for b in range(n_distinct)]
     mbatches = [marshalled[i % n_distinct] for i in range(n_steps)]
-    log("rank %d: %d reads generated (%.1fs), %d host threads" % (rank, len(seqs), time.time() - t1, n_threads))
+
+    def batch_lists(b):
+        """distinct batch b as (names, list of bytes), for the --full legs"""
+        return names[b * rps:(b + 1) * rps], [blob[i * rlen:(i + 1) * rlen].tobytes() for i in range(b * rps, (b + 1) * rps)]
+    log("rank %d: %d reads generated (%.1fs), %d host threads" % (rank, n_reads, time.time() - t1, n_threads))
+
+    import torch
+    dist = None
+    if world > 1 or os.environ.get("WM_BENCH_FORCE_DIST"):     # (the env switch lets a 1-GPU box exercise the RCCL code path)
+        import torch.distributed as dist
+        if torch.cuda.device_count() <= local:
+            sys.exit("bench.py: rank %d has no GPU %d (%d visible)" % (rank, local, torch.cuda.device_count()))
+        torch.cuda.set_device(local)
+        dist.init_process_group("nccl", device_id=torch.device("cuda", local))
+        assert dist.get_world_size() == args.gpus and dist.get_backend() == "nccl"
+
+    # ---- index: rank 0 builds, RCCL broadcasts the flat arrays ----
+    # device contexts (own streams + arena each: that many batched calls are on the device at once) share the 288 GB of HBM
+    n_ctx = int(os.environ.setdefault("WM_CONTEXTS", "6"))
+    arena = int(float(os.environ.get("WM_BENCH_ARENA_GB", min(48.0, 216.0 / n_ctx))) * (1 << 30))
+    ctx = gpu.Context(local, arena)
+    if rank == 0:
+        ref, fa, kf = make_workload(args.ref_mb, tmp, ctx, ref)
+        t_i = time.time()
+        idx, ist = gpu.Index.build_on_device(ctx, fa, kf, k=15, w=50, n_threads=min(64, n_cores))      # map-ont and map-pb: k=15, w=50 (src/options.c:94-103)
+        log("index: %d minimizers, built in %.1fs (reference sketched on the device in %.2fs)" % (idx.n_minimizers, time.time() - t_i, ist["device_sketch_s"]))
+    if dist is not None:
+        dev = torch.device("cuda", local)
+        idx, uploaded = wmdist.broadcast_index(idx if rank == 0 else None, rank, dist, dev, ctx)      # RCCL over xGMI, one broadcast per flat array, received straight into the context
+    if dist is None or not uploaded:
+        idx.upload(ctx)
+    os.environ.setdefault("WM_READ_SLABS", str(max(1, min(4, int(os.environ.get("WM_BENCH_SLOTS", 2))))))      # resident read slabs = mini-batches in flight (below)
+    mapper = gpu.Mapper(ctx, idx, cfg["preset"], gpu.MM_F_CIGAR | gpu.MM_F_OUT_CG)
+    if n_threads > 1:
+        mapper.set_threads(n_threads, arena)
 
     def sync():
         if dist is not None:
@@ -402,8 +495,9 @@ def main():
     import threading
     n_slots = max(1, min(4, int(os.environ.get("WM_BENCH_SLOTS", 2)))) if int(os.environ.get("WM_BENCH_PIPELINE", 1)) else 1
 
-    def run_steps(step_batches):
-        """maps the given mini-batches on n_slots lanes (each lane takes the next unmapped step, like wm_map_file's lanes); returns (hits, bases)"""
+    def run_steps(step_batches, last=None):
+        """maps the given mini-batches on n_slots lanes (each lane takes the next unmapped step, like wm_map_file's lanes); returns (hits, bases).
+        `last` (a dict) receives what Mapper.map returned for the last of the batches: text length, hits, first hit of each read."""
         tot = [0] * n_slots
         err = []
         nxt = [0]
@@ -417,8 +511,10 @@ def main():
                         nxt[0] += 1
                     if i >= len(step_batches):
                         break
-                    _, h, _, _ = mapper.map(step_batches[i], copy_text=False, slot=s)        # the records stay in the library's buffer (no Python copy)
+                    tl, h, _, fh = mapper.map(step_batches[i], copy_text=False, slot=s)        # the records stay in the library's buffer (no Python copy)
                     tot[s] += len(h)
+                    if last is not None and i == len(step_batches) - 1:
+                        last.update(tlen=tl, hits=h, first=fh)
             except Exception as e:  # noqa: BLE001
                 err.append(e)
         th = [threading.Thread(target=worker, args=(s,)) for s in range(n_slots)]
@@ -447,7 +543,8 @@ def main():
         import signal
         os.kill(os.getpid(), signal.SIGUSR2)
     t_start = time.time()
-    hits, bases = run_steps(mbatches[args.warmup:])
+    last = {}
+    hits, bases = run_steps(mbatches[args.warmup:], last)
     sync()
     elapsed = time.time() - t_start
     ru1 = resource.getrusage(resource.RUSAGE_SELF)
@@ -479,14 +576,17 @@ def main():
         out["host"]["host_bound_gbps_node"] = round(n_cores / max(cpu_per_base, 1e-12) / 1e9, 4)
         out["host"]["predicted_8rank_gbps"] = round(min(8 * out["value"] / max(1, world), n_cores / max(cpu_per_base, 1e-12) / 1e9), 4)
         out["host"]["predicted_8rank_note"] = "min(8 x the per-rank rate of this run, usable cores / CPU-s per base): with %d usable cores the host side caps an 8-rank node here; not a measurement" % n_cores
-        if world == 1 and int(os.environ.get("WM_BENCH_FILE", 1)):
+        if args.dump_outputs and last:
+            dump_outputs(args.dump_outputs, last["tlen"], last["hits"], last["first"])
+        if args.full and world == 1 and int(os.environ.get("WM_BENCH_FILE", 1)):
             # the drop-in path: reads.fa -> out.paf through wm_map_file (reader / two mapping lanes / ordered writer, host/wm_pipeline.cpp) on the
             # mini-batches of the timed region: FASTA parsing and record output inside the clock, as in the reference's mapping phase (src/map.c:1107-1224)
             try:
-                nb = min(2, len(distinct))
+                nb = min(2, n_distinct)
                 rq_f = os.path.join(tmp, "f2f_reads.fa")
                 fn, fs_ = [], []
-                for d_ in distinct[:nb]:
+                for b in range(nb):
+                    d_ = batch_lists(b)
                     fn += d_[0]; fs_ += d_[1]
                 write_reads_fasta(rq_f, fn, fs_)
                 fbases = sum(len(x) for x in fs_)
@@ -501,9 +601,9 @@ def main():
                 log("file to file: %d reads, %.2f s = %.4f Gbp/s (read %.2f map %.2f write %.2f s)" % (len(fs_), wall_f, fbases / wall_f / 1e9, st_f["t_read"], st_f["t_map"], st_f["t_write"]))
             except Exception as e:  # noqa: BLE001
                 log("file-to-file leg error:", repr(e))
-        if world == 1 and args.cpu_sample != 0:
+        if args.full and world == 1 and args.cpu_sample != 0:
             # one full step (the first timed batch) through the REAL reference on this host's cores: CPU baseline + parity
-            bn, bs = batches[args.warmup]
+            bn, bs = batch_lists(args.warmup % n_distinct)
             if args.cpu_sample > 0:
                 bn, bs = bn[:args.cpu_sample], bs[:args.cpu_sample]
             try:
@@ -529,6 +629,7 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+    shutil.rmtree(tmp, ignore_errors=True)      # the reference FASTA, the -W list and what --full wrote
 
 
 if __name__ == "__main__":

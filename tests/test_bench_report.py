@@ -80,3 +80,26 @@ def test_parity_diff_masks_mapq_and_rl_only_on_the_mcas_path():
     d = parity.diff_texts(sam_ref, sam_our, sam=True)
     assert d["mismatches"] == 0 and d["mapq_compared"] == 1
     assert parity.diff_texts(sam_ref, sam_our.replace(b"\t17\t", b"\t16\t"), sam=True)["mismatches"] == 1
+
+
+def test_reads_do_not_depend_on_the_process_count_and_the_dump_stays_under_64_mb(tmp_path):
+    import ctypes as C
+    import numpy as np
+    B = _bench()
+    ref = B.synth.make_reference(2, 200000, 3, repeat_frac=0.1)
+    n, rlen, cfg = 2 * B.READ_CHUNK + 5, 2000, B.CONFIGS[2]
+    blob = B.make_read_blob(ref, n, rlen, 4, cfg, 1)
+    assert np.array_equal(blob, B.make_read_blob(ref, n, rlen, 4, cfg, 3))
+    # chunk c holds synth.make_reads of seed (seed, c)
+    r, _ = B.synth.make_reads(ref, 5, rlen, [4, 2], profile=cfg["profile"], sv_frac=cfg["sv_frac"])
+    assert blob[2 * B.READ_CHUNK * rlen:].tobytes() == b"".join(B.synth.codes_to_ascii(x) for x in r)
+    names = [b"r%d" % i for i in range(n)]
+    k, nm, sq, lens, _ = B.marshal_blob(names[10:20], blob, 10, 10, rlen)
+    assert k == 10 and nm[3] == b"r13" and C.string_at(sq[3], rlen) == blob[13 * rlen:14 * rlen].tobytes() and list(lens) == [rlen] * 10
+    hits = np.arange(500000 * 16, dtype=np.int32).reshape(-1, 16)
+    first = np.arange(65537, dtype=np.int64)
+    B.dump_outputs(str(tmp_path), 12345, hits, first)
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) < 64_000_000
+    rows = np.load(tmp_path / "hits_rows.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "hits.npy"), hits[rows].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "first.npy"), first) and np.load(tmp_path / "text_bytes.npy")[0] == 12345
