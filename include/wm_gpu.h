@@ -242,9 +242,23 @@ int wm_sketch_batch(wm_ctx_t *ctx, int n, const uint8_t *seqs, size_t seqs_bytes
  * link-level substitute of mm_sketch (src/mmpriv.h:61) needs: see oracle/wm_subst.cpp. */
 int wm_sketch_set_filter(wm_ctx_t *ctx, const uint8_t *bits, size_t n_bytes, uint64_t table_bits, uint32_t salt0, uint32_t salt1, int k, int w);
 /* collect_seed_hits: minimizers of job i are mini[mini_off[i] .. +n_mini[i]); anchors (sorted by x with the
- * reference's radix_sort_128x permutation) go to out[out_off[i] .. +n_anchors[i]); rep_len as src/map.c:126. */
+ * reference's radix_sort_128x permutation) go to out[out_off[i] .. +n_anchors[i]); rep_len as src/map.c:126.
+ * flag: MM_F_FOR_ONLY / MM_F_REV_ONLY are honoured. MM_F_NO_DIAG (0x1) / MM_F_NO_DUAL (0x2) are IGNORED here, as skip_seed
+ * (src/map.c:132-154) ignores them when qname == NULL (:135): this entry point has no query names. See wm_seed_batch_keyed. */
 int wm_seed_batch(wm_ctx_t *ctx, int n, const wm128_t *mini, const uint64_t *mini_off, const int32_t *n_mini, const int32_t *qlen,
                   int max_occ, int64_t flag, wm128_t *out, size_t out_cap, uint64_t *out_off, int32_t *n_anchors, int32_t *rep_len);
+/* Self / all-vs-all mapping (-D, --dual=no, -X): skip_seed (src/map.c:132-154) compares the query's name with the name of every contig it
+ * hits. The device compares integers: wm_index_upload ranks the distinct contig names in strcmp order, and wm_index_query_key turns a query
+ * name into its key for that index — lo = distinct contig names that are strcmp-smaller, eq = the name occurs among the contigs — so that
+ * strcmp(qname, contig) == 0 <=> eq && rank(contig) == lo and > 0 <=> rank(contig) < lo. One binary search per read; a key belongs to the index
+ * it was made for (every part of a split index has its own). */
+typedef struct { uint32_t lo, eq; } wm_qkey_t;
+int wm_index_query_key(const wm_index_t *idx, const char *qname, wm_qkey_t *key);
+/* wm_seed_batch with one key per job: MM_F_NO_DIAG drops the anchors on the diagonal of a contig that has the query's name AND qlen[i] bases
+ * and marks the other same-strand anchors on it MM_SEED_SELF (bit 43 of y); MM_F_NO_DUAL drops the anchors on contigs whose name is smaller
+ * than the query's (src/map.c:132-154). keys == NULL: wm_seed_batch. */
+int wm_seed_batch_keyed(wm_ctx_t *ctx, int n, const wm128_t *mini, const uint64_t *mini_off, const int32_t *n_mini, const int32_t *qlen, const wm_qkey_t *keys,
+                        int max_occ, int64_t flag, wm128_t *out, size_t out_cap, uint64_t *out_off, int32_t *n_anchors, int32_t *rep_len);
 /* mm_chain_dp (src/mmpriv.h:73) for n anchor sets; chains of job i: u[u_off[i] .. +n_u[i]), anchors regrouped in
  * place: a[a_off[i] .. +n_v[i]). */
 typedef struct { int32_t max_dist_x, min_dist_x, max_dist_y, bw, max_skip, max_iter, min_cnt, min_sc; float gap_scale;
@@ -268,6 +282,11 @@ typedef struct {
 typedef struct { int32_t n_anchors, rep_len, n_mini, n_u, n_v; uint32_t u_off, a_off; } wm_window_res_t;
 int wm_window_batch(wm_ctx_t *ctx, int n, const wm_window_job_t *jobs, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
                     int max_occ, int64_t flag, wm_window_res_t *res, uint64_t *u_pool, size_t u_cap, size_t *u_used, wm128_t *a_pool, size_t a_cap, size_t *a_used);
+/* flag: as wm_seed_batch — MM_F_NO_DIAG / MM_F_NO_DUAL are ignored without query names (skip_seed with qname == NULL, src/map.c:132-154).
+ * wm_window_batch_keyed: one key per job (wm_index_query_key), the two bits are served; the length skip_seed compares a contig's with is
+ * jobs[i].len, the sequence the job seeds (inside stage 1 a window's: qlen_sum of src/map.c:346-364). keys == NULL: wm_window_batch. */
+int wm_window_batch_keyed(wm_ctx_t *ctx, int n, const wm_window_job_t *jobs, const wm_qkey_t *keys, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
+                          int max_occ, int64_t flag, wm_window_res_t *res, uint64_t *u_pool, size_t u_cap, size_t *u_used, wm128_t *a_pool, size_t a_cap, size_t *a_used);
 /* kernel time of the last sketch/seed/chain/window batch call (HIP events on the context stream), ms */
 float wm_last_aux_ms(const wm_ctx_t *ctx);
 

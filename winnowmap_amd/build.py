@@ -119,6 +119,20 @@ def build_emu(defines=()):
     return out
 
 
+def build_emu_selfmap():
+    """tests/simt_emu/libwm_emu_selfmap.so: the two seeding kernels with the name tables of self / all-vs-all mapping and the host's name ranking
+    on the emulator (tests/simt_emu/emu_selfmap.cpp)."""
+    emu = os.path.join(ROOT, "tests", "simt_emu")
+    out = os.path.join(emu, "libwm_emu_selfmap.so")
+    srcs = [os.path.join(emu, f) for f in ("emu_selfmap.cpp", "simt.h")] + \
+           [os.path.join(CSRC, f) for f in ("seedchain_kernel.h", "window_kernel.h", "wm_internal.h", os.path.join("host", "wm_names.h"))]
+    with _Lock(out):
+        if _newer(out, srcs):
+            _run_to(out, lambda o: ["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
+                                    "-I" + emu, "-I" + CSRC, "-o", o, os.path.join(emu, "emu_selfmap.cpp")])
+    return out
+
+
 def build_emu_stripe(defines=()):
     """tests/simt_emu/libwm_emu_stripe[_<defines>].so: the stripe-pipelined ksw kernel alone on the emulator, with its event counters and the
     polling watchdog (tests/simt_emu/emu_stripe.cpp). ("WM_STRIPE_TEST_SLACK=...",) builds the variant whose bookkeeping margin is useless, so that
@@ -167,6 +181,7 @@ if __name__ == "__main__":
     build_gpu(force="--force" in sys.argv, verbose=True)
     build_oracle()
     build_emu()
+    build_emu_selfmap()
     build_emu_stripe()
     build_emu_chain()
     build_harness()

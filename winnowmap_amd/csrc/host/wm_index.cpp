@@ -512,6 +512,20 @@ int index_build_parts_from_fasta(const IdxOpt &io, const std::string &fasta, con
 	return (int)parts.size();
 }
 
+const NameTable &Index::name_table() const
+{
+	static std::mutex mu;
+	std::lock_guard<std::mutex> lk(mu);
+	if (!names_ || names_->rank.size() != seq.size())
+		names_ = std::make_shared<const NameTable>(rank_names(seq.size(), [&](uint32_t i) { return seq[i].name.c_str(); }));
+	return *names_;
+}
+
+NameKey Index::name_key(const char *qname) const
+{
+	return wm::name_key(name_table(), [&](uint32_t i) { return seq[i].name.c_str(); }, qname);
+}
+
 int32_t Index::cal_max_occ(float f) const
 {
 	if (f <= 0.) return INT32_MAX;

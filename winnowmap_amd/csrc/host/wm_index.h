@@ -3,6 +3,8 @@
 // maps to its reference positions in ascending order (src/index.c:88-105,239).
 #pragma once
 #include "wm_core.h"
+#include "wm_names.h"
+#include <memory>
 
 namespace wm {
 
@@ -51,6 +53,10 @@ struct Index {
 	bool has_junc() const { return !I.empty(); }
 	int bed_junc(int32_t ctg, int32_t st, int32_t en, uint8_t *s) const;
 	int32_t cal_max_occ(float f) const;                            // mm_idx_cal_max_occ, src/index.c:173-194
+	// the contig names as integers (wm_names.h: skip_seed's strcmp on the device)
+	const NameTable &name_table() const;                           // built from seq[].name on first use (every way an index comes to be ends with its names in place)
+	NameKey name_key(const char *qname) const;
+	mutable std::shared_ptr<const NameTable> names_;
 	static uint64_t slot_of(uint64_t key, int hbits) { return (key * 0x9E3779B97F4A7C15ULL) >> (64 - hbits); }
 };
 

@@ -29,7 +29,7 @@ inline uint32_t read_hash(const char *qname, int qlen, int seed)
 // One window from its codes to aligned regions: sketch → seed → [anchors handed in] → chain in ONE device call (WindowReq), then region
 // generation + alignment + MAPQ on the chains (src/map.c:69-84, 222-254, 375-430 and :880-933)
 void window_and_align(Scheduler &sch, const Index &idx, const MapOpt &o, float gap_scale, const uint8_t *seq_codes, int64_t seq_dev_off, bool sketch_it,
-                      const uint8_t *codes, int64_t dev_off, int qlen, uint32_t hash, std::vector<m128> &&pre, int *rep_len_io, Segment &out, int *frag_gap)
+                      const uint8_t *codes, int64_t dev_off, int qlen, uint32_t hash, std::vector<m128> &&pre, int *rep_len_io, Segment &out, int *frag_gap, const NameKey *key)
 {
 	const int max_gap_qry = o.max_gap;
 	int max_gap_ref;
@@ -43,6 +43,7 @@ void window_and_align(Scheduler &sch, const Index &idx, const MapOpt &o, float g
 	if (sketch_it) { wr.seq = seq_codes; wr.len = qlen; wr.dev_off = seq_dev_off; }
 	wr.pre = std::move(pre);
 	wr.max_occ = o.mid_occ; wr.flag = o.flag;
+	if (key) { wr.has_key = true; wr.q_lo = key->lo; wr.q_eq = key->eq; }          // skip_seed (src/map.c:132-154): the read's name against the contigs'; qlen there = this request's len
 	wr.max_dist_x = max_gap_ref; wr.min_dist_x = min_gap_ref; wr.max_dist_y = max_gap_qry; wr.bw = o.bw;
 	wr.max_skip = o.max_chain_skip; wr.max_iter = o.max_chain_iter; wr.min_cnt = o.min_cnt; wr.min_sc = o.min_chain_score;
 	wr.gap_scale = gap_scale;
@@ -76,6 +77,7 @@ struct ReadTask {
 	const uint8_t *codes = 0;                    // 0..4 codes of the read (inside the mini-batch's code buffer)
 	int64_t dev_off = -1;                        // where they live on the device (DeviceOps::load_reads), -1 = not resident
 	int qlen = 0;
+	NameKey key; bool has_key = false;           // the read's name as a key of this index (F_NO_DIAG / F_NO_DUAL: every window request of the read carries it)
 	std::vector<std::vector<m128>> collect;     // MCAS anchors per suffix position (collect_a, src/map.c:296)
 	std::vector<uint8_t> mapped;                 // seqMapped, src/map.c:310
 	int pending = 0;
@@ -94,7 +96,7 @@ void stage1_position(Scheduler &sch, const Index &idx, const MapOpt &opt, const 
 			Segment S;
 			int rep_len = 0;
 			const int64_t dev = T.dev_off >= 0 ? T.dev_off + start : -1;
-			window_and_align(sch, idx, o2, opt.chain_gap_scale, T.codes + start, dev, true, T.codes + start, dev, sub_len, read_hash(qname, sub_len, o2.seed), std::vector<m128>(), &rep_len, S, 0);
+			window_and_align(sch, idx, o2, opt.chain_gap_scale, T.codes + start, dev, true, T.codes + start, dev, sub_len, read_hash(qname, sub_len, o2.seed), std::vector<m128>(), &rep_len, S, 0, T.has_key ? &T.key : 0);
 			for (const Reg &r : S.regs) {
 				if ((int)r.mapq >= o2.min_mapq && r.blen >= o2.min_qcov * sub_len && r.cnt > 0) {
 					found = true;
@@ -145,12 +147,12 @@ void stage2(Scheduler &sch, const Index &idx, const MapOpt &opt, ReadTask &T)
 	if (!a.empty() && unmapped > 0) {                                  // seeds from the stretches stage 1 left unmapped join the collected anchors (:786-846)
 		std::vector<uint8_t> masked(T.codes, T.codes + L);
 		for (int i = 0; i < L; ++i) if (T.mapped[i]) masked[i] = 4;
-		window_and_align(sch, idx, o3, opt.chain_gap_scale, masked.data(), -1, true, T.codes, T.dev_off, L, hash, std::move(a), &rep_len, S, &frag_gap);   // (a masked copy: not resident)
+		window_and_align(sch, idx, o3, opt.chain_gap_scale, masked.data(), -1, true, T.codes, T.dev_off, L, hash, std::move(a), &rep_len, S, &frag_gap, T.has_key ? &T.key : 0);   // (a masked copy: not resident)
 	} else if (a.empty()) {                                            // plain minimap2-style mapping with the user's options (:849-865)
 		o3 = opt;
-		window_and_align(sch, idx, o3, opt.chain_gap_scale, T.codes, T.dev_off, true, T.codes, T.dev_off, L, hash, std::vector<m128>(), &rep_len, S, &frag_gap);
+		window_and_align(sch, idx, o3, opt.chain_gap_scale, T.codes, T.dev_off, true, T.codes, T.dev_off, L, hash, std::vector<m128>(), &rep_len, S, &frag_gap, T.has_key ? &T.key : 0);
 	} else                                                             // the collected anchors cover the read: chain them as they are
-		window_and_align(sch, idx, o3, opt.chain_gap_scale, 0, -1, false, T.codes, T.dev_off, L, hash, std::move(a), &rep_len, S, &frag_gap), T.out->rep_len_defined = false;
+		window_and_align(sch, idx, o3, opt.chain_gap_scale, 0, -1, false, T.codes, T.dev_off, L, hash, std::move(a), &rep_len, S, &frag_gap, T.has_key ? &T.key : 0), T.out->rep_len_defined = false;
 	T.out->regs = std::move(S.regs);
 	T.out->rep_len = rep_len;
 	T.out->frag_gap = frag_gap;
@@ -227,6 +229,10 @@ void map_batch(const Index &idx, const MapOpt &opt, DeviceOps *ops, const std::v
 	for (size_t i = 0; i < reads.size(); ++i) {
 		tasks[i].in = &reads[i]; tasks[i].out = &out[i]; tasks[i].qlen = (int)reads[i].seq.size();
 		tasks[i].codes = codes_all.get() + code_off[i]; tasks[i].dev_off = resident ? dev_base + (int64_t)code_off[i] : -1;
+	}
+	if (opt.flag & (F_NO_DIAG | F_NO_DUAL)) {                            // -D / --dual=no / -X: one binary search per read, against THIS index's names (a part of a split index has its own)
+		idx.name_table();
+		parallel_for(T, reads.size(), [&](size_t i) { tasks[i].key = idx.name_key(reads[i].name.c_str()); tasks[i].has_key = true; });
 	}
 	// reads in flight over all workers (WM_INFLIGHT): large enough for full device batches at every stage, small enough that the
 	// stages overlap instead of running in lock-step phases

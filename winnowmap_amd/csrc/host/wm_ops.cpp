@@ -20,6 +20,7 @@ void DeviceOps::window_batch(int w, int k, std::vector<WindowReq*> &reqs)
 		for (size_t j = i; j < n; ++j)
 			if (!done[j] && reqs[j]->len > 0 && !sk[j].mini.empty() && reqs[j]->max_occ == reqs[i]->max_occ && reqs[j]->flag == reqs[i]->flag) {
 				sd[j].mini = sk[j].mini.data(); sd[j].n_mini = (int)sk[j].mini.size(); sd[j].qlen = reqs[j]->len; sd[j].max_occ = reqs[j]->max_occ; sd[j].flag = reqs[j]->flag;
+				sd[j].has_key = reqs[j]->has_key; sd[j].q_lo = reqs[j]->q_lo; sd[j].q_eq = reqs[j]->q_eq;
 				grp.push_back(&sd[j]); done[j] = 1;
 			}
 		seed_batch(grp);

@@ -22,6 +22,9 @@ struct SeedReq {                   // collect_seed_hits (src/map.c:222-254): loo
 	const m128 *mini = 0; int n_mini = 0; int qlen = 0; int max_occ = 0; int64_t flag = 0;
 	std::vector<m128> a;           // out: anchors sorted with radix_sort_128x
 	int rep_len = 0;               // out (src/map.c:111-116,126)
+	// name key of the query for this index (Index::name_key): with it F_NO_DIAG / F_NO_DUAL in `flag` are served (skip_seed, src/map.c:132-154);
+	// without it they are ignored, as the reference ignores them for qname == NULL
+	bool has_key = false; uint32_t q_lo = 0, q_eq = 0;
 };
 
 struct ChainReq {                  // mm_chain_dp (src/chain.c:22); consumes `a`
@@ -47,6 +50,7 @@ struct WindowReq {
 	std::vector<m128> a;                   // out: anchors grouped by chain
 	std::vector<uint64_t> u;               // out: score<<32 | count per chain
 	int rep_len = 0, n_anchors = 0;        // out: src/map.c:126; anchors before chaining
+	bool has_key = false; uint32_t q_lo = 0, q_eq = 0;   // name key of the read, as SeedReq; the length skip_seed compares is `len` (a window's inside stage 1)
 };
 
 struct KswReq {                    // ksw_extd2_sse (src/ksw2.h:60)

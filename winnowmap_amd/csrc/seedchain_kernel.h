@@ -20,6 +20,34 @@
 namespace wmk {
 using namespace simt;
 
+// skip_seed (src/map.c:132-154) for one occurrence r = rid << 32 | pos << 1 | strand of a query minimizer at q_pos = pos << 1 | strand; returns "skip".
+// flag: MM_F_NO_DIAG 0x1 | MM_F_NO_DUAL 0x2 | MM_F_FOR_ONLY 0x100000 | MM_F_REV_ONLY 0x200000, wave-uniform; a job without a name key carries neither
+// of the first two (the reference's qname == NULL, :135). strcmp(qname, contig name) never reaches the device: the host ranks the distinct contig
+// names (ix.name_rank) and turns the query's name into (q_lo, q_eq) = (distinct contig names below it, it is one of them), host/wm_index.h, so
+//   cmp == 0  <=>  q_eq && name_rank[rid] == q_lo        cmp > 0  <=>  name_rank[rid] < q_lo
+// qlen is the length of the sequence THIS job seeds (a window's inside stage 1: qlen_sum of src/map.c:346-364), as in the reference.
+// self: the anchor gets MM_SEED_SELF (bit 43 of y, src/map.c:247). The rid of neighbouring occurrences differs in all-vs-all (one hit per overlapping
+// read), so the two table reads are scattered 4-byte gathers: both are issued before either is used.
+WM_DEV vbool seed_skip(const wm_index_view_t &ix, int flag, uint32_t q_lo, int q_eq, int qlen, const V<uint64_t> r, const V<uint32_t> q_pos, vbool &self)
+{
+	const vbool fwd = cast<uint32_t>(r & (uint64_t)1) == (q_pos & 1u);
+	vbool skip = fwd != fwd;                                             // false
+	self = skip;
+	if (flag & 3) {
+		const V<uint64_t> rid = r >> 32;
+		const V<uint32_t> rk = gld(ix.name_rank, rid), rl = gld(ix.seq_len, rid);
+		if (flag & 1) {                                                   // :141-144
+			const vbool same = rk == q_lo && q_eq != 0 && rl == (uint32_t)qlen;
+			skip = same && (cast<uint32_t>(r & (uint64_t)0xffffffffu) >> 1) == (q_pos >> 1);
+			self = same && fwd && !skip;
+		}
+		if (flag & 2) skip = skip || rk < q_lo;                           // :145-146
+	}
+	if (flag & (0x100000 | 0x200000))                                     // :148-154
+		skip = skip || (fwd && (flag & 0x200000) != 0) || (!fwd && (flag & 0x100000) != 0);
+	return skip;
+}
+
 WM_DEV void seed_wave(const wm_index_view_t ix, const wm_seed_job_t jb, const wm128_t *mini_pool, wm128_t *anchor_pool,
                       int *occ_scratch /* n_mini ints */, wm_seed_res_t *res)
 {
@@ -27,7 +55,7 @@ WM_DEV void seed_wave(const wm_index_view_t ix, const wm_seed_job_t jb, const wm
 	const uint64_t *mini = (const uint64_t*)(mini_pool + jb.mini_off);
 	uint64_t *outp = (uint64_t*)(anchor_pool + jb.out_off);
 	const uint64_t hmask = ((uint64_t)1 << ix.hbits) - 1;
-	const bool strand_filter = (jb.flag & (0x100000 | 0x200000)) != 0;
+	const int filt = jb.flag & (0x100000 | 0x200000 | 3);     // skip_seed has something to do (wave-uniform; 0 on the default path)
 	int base = 0;                                        // anchors written so far
 	for (int m0 = 0; m0 < jb.n_mini; m0 += 64) {
 		const V<int> m = ln + m0;
@@ -54,14 +82,12 @@ WM_DEV void seed_wave(const wm_index_view_t ix, const wm_seed_job_t jb, const wm
 		WM_END
 		// occurrence filter + (optional) strand filter decide how many anchors each minimizer contributes
 		V<int> emit = sel(have && cnt < jb.max_occ, cnt, 0);
-		WM_IF(strand_filter && emit > 0)
+		WM_IF(filt != 0 && emit > 0)
 			V<int> kept = 0;
-			const V<int> qstrand = cast<int>(my & (uint64_t)1);
 			for (int h = 0; h < jb.max_occ && any(emit > h); ++h)
 				WM_IF(emit > h)
-					const V<int> rstrand = cast<int>(gld(ix.P, first + (uint64_t)h) & (uint64_t)1);
-					const vbool fwd = rstrand == qstrand;
-					kept = kept + sel((fwd && !(jb.flag & 0x200000)) || (!fwd && !(jb.flag & 0x100000)), 1, 0);
+					vbool self = emit != emit;
+					kept = kept + sel(seed_skip(ix, filt, jb.q_lo, jb.q_eq, jb.qlen, gld(ix.P, first + (uint64_t)h), cast<uint32_t>(my), self), 0, 1);
 				WM_END
 			emit = kept;
 		WM_END
@@ -82,8 +108,8 @@ WM_DEV void seed_wave(const wm_index_view_t ix, const wm_seed_job_t jb, const wm
 					const V<uint64_t> r = gld(ix.P, first + (uint64_t)h);
 					const V<uint64_t> rpos = (r & (uint64_t)0xffffffffu) >> 1;
 					const vbool fwd = cast<uint32_t>(r & (uint64_t)1) == (q_pos & 1u);
-					vbool keep = rpos == rpos;
-					if (strand_filter) keep = (fwd && !(jb.flag & 0x200000)) || (!fwd && !(jb.flag & 0x100000));
+					vbool keep = rpos == rpos, self = rpos != rpos;
+					if (filt) keep = !seed_skip(ix, filt, jb.q_lo, jb.q_eq, jb.qlen, r, q_pos, self);
 					WM_IF(keep)
 						V<uint64_t> ax = (r & (uint64_t)0xffffffff00000000ULL) | rpos;
 						V<uint64_t> ay = cast<uint64_t>(q_span) << 32;
@@ -92,6 +118,7 @@ WM_DEV void seed_wave(const wm_index_view_t ix, const wm_seed_job_t jb, const wm
 							ay = ay | cast<uint64_t>(cast<uint32_t>(V<int>(jb.qlen) - cast<int>((q_pos >> 1) + 1u - q_span) - 1));
 						WM_END
 						ay = sel(tandem, ay | ((uint64_t)1 << 42), ay);
+						if (filt & 1) ay = sel(self, ay | ((uint64_t)1 << 43), ay);      // MM_SEED_SELF
 						WM_IF(w < jb.cap) gst(outp, w * 2, ax); gst(outp, w * 2 + 1, ay); WM_END
 						w = w + 1;
 					WM_END

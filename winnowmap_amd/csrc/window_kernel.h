@@ -47,7 +47,7 @@ WM_DEV void win_seed_wave(const wm_index_view_t ix, const wm_win_job_t jb, const
 	const V<int> ln = lane();
 	const uint64_t *mini = (const uint64_t*)mini_;
 	const uint64_t hmask = ((uint64_t)1 << ix.hbits) - 1;
-	const bool strand_filter = (jb.seed_flag & (0x100000 | 0x200000)) != 0;
+	const int filt = jb.seed_flag & (0x100000 | 0x200000 | 3);         // skip_seed (seedchain_kernel.h) has something to do: wave-uniform, 0 on the default path
 	int total = 0, rep_len = 0, carry_en = 0;
 	for (int m0 = 0; m0 < n_mini; m0 += 64) {
 		const V<int> m = ln + m0;
@@ -72,14 +72,12 @@ WM_DEV void win_seed_wave(const wm_index_view_t ix, const wm_win_job_t jb, const
 			}
 		WM_END
 		V<int> emit = sel(have && cnt < jb.max_occ, cnt, 0);
-		WM_IF(strand_filter && emit > 0)
+		WM_IF(filt != 0 && emit > 0)                                       // the occurrences skip_seed keeps (src/map.c:237), so that the wave can take its slots with one atomic
 			V<int> kept = 0;
-			const V<int> qstrand = cast<int>(my & (uint64_t)1);
 			for (int h = 0; h < jb.max_occ && any(emit > h); ++h)
 				WM_IF(emit > h)
-					const V<int> rstrand = cast<int>(gld(ix.P, first + (uint64_t)h) & (uint64_t)1);
-					const vbool fwd = rstrand == qstrand;
-					kept = kept + sel((fwd && !(jb.seed_flag & 0x200000)) || (!fwd && !(jb.seed_flag & 0x100000)), 1, 0);
+					vbool self = emit != emit;
+					kept = kept + sel(seed_skip(ix, filt, jb.q_lo, jb.q_eq, jb.len, gld(ix.P, first + (uint64_t)h), cast<uint32_t>(my), self), 0, 1);
 				WM_END
 			emit = kept;
 		WM_END
@@ -131,8 +129,8 @@ WM_DEV void win_seed_wave(const wm_index_view_t ix, const wm_win_job_t jb, const
 					const V<uint64_t> r = gld(ix.P, first + (uint64_t)h);
 					const V<uint64_t> rpos = (r & (uint64_t)0xffffffffu) >> 1;
 					const vbool fwd = cast<uint32_t>(r & (uint64_t)1) == (q_pos & 1u);
-					vbool keep = rpos == rpos;
-					if (strand_filter) keep = (fwd && !(jb.seed_flag & 0x200000)) || (!fwd && !(jb.seed_flag & 0x100000));
+					vbool keep = rpos == rpos, self = rpos != rpos;
+					if (filt) keep = !seed_skip(ix, filt, jb.q_lo, jb.q_eq, jb.len, r, q_pos, self);
 					WM_IF(keep)
 						V<uint64_t> ax = (r & (uint64_t)0xffffffff00000000ULL) | rpos;
 						V<uint64_t> ay = cast<uint64_t>(q_span) << 32;
@@ -141,6 +139,7 @@ WM_DEV void win_seed_wave(const wm_index_view_t ix, const wm_win_job_t jb, const
 							ay = ay | cast<uint64_t>(cast<uint32_t>(V<int>(jb.len) - cast<int>((q_pos >> 1) + 1u - q_span) - 1));
 						WM_END
 						ay = sel(tandem, ay | ((uint64_t)1 << 42), ay);
+						if (filt & 1) ay = sel(self, ay | ((uint64_t)1 << 43), ay);      // MM_SEED_SELF (src/map.c:247)
 						gst(outp, w * 2, ax); gst(outp, w * 2 + 1, ay);
 						w = w + 1;
 					WM_END

@@ -365,6 +365,22 @@ extern "C" int wm_index_seq_len(const wm_index_t *h, int rid) { return (int)h->i
 extern "C" uint64_t wm_index_n_minimizers(const wm_index_t *h) { return h->ix.n_minimizers; }
 extern "C" const uint64_t *wm_index_get(const wm_index_t *h, uint64_t minier, int *n) { return h->ix.get(minier, n); }
 
+// rank of every contig's name, then every contig's length (wm_ctx_s::d_name_rank / d_seq_len)
+static std::vector<uint32_t> name_tables(const wm::Index &ix)
+{
+	std::vector<uint32_t> t(ix.name_table().rank);
+	for (const wm::RefSeq &r : ix.seq) t.push_back(r.len);
+	return t;
+}
+
+extern "C" int wm_index_query_key(const wm_index_t *h, const char *qname, wm_qkey_t *key)
+{
+	if (!h || !qname || !key) return set_err(WM_EINVAL, "null argument");
+	const wm::NameKey k = h->ix.name_key(qname);
+	key->lo = k.lo; key->eq = k.eq;
+	return WM_OK;
+}
+
 extern "C" int wm_index_upload(wm_ctx_t *c, const wm_index_t *h)
 {
 	if (!c || !h) return set_err(WM_EINVAL, "null argument");
@@ -372,24 +388,27 @@ extern "C" int wm_index_upload(wm_ctx_t *c, const wm_index_t *h)
 	const wm::Index &ix = h->ix;
 	if (ix.bloom.table_bits >= ((uint64_t)1 << 32)) return set_err(WM_EINVAL, "bloom table of %llu bits not supported on device", (unsigned long long)ix.bloom.table_bits);
 	// (new arrays first; the old index goes only when the new one is complete — as wm_index_upload_dev)
-	uint64_t *n_hkey = 0, *n_hval = 0, *n_P = 0; uint8_t *n_bloom = 0; uint32_t *n_S = 0;
-	auto drop = [&]() { hipFree(n_hkey); hipFree(n_hval); hipFree(n_P); hipFree(n_bloom); hipFree(n_S); (void)hipGetLastError(); };
+	uint64_t *n_hkey = 0, *n_hval = 0, *n_P = 0; uint8_t *n_bloom = 0; uint32_t *n_S = 0, *n_names = 0;
+	auto drop = [&]() { hipFree(n_hkey); hipFree(n_hval); hipFree(n_P); hipFree(n_bloom); hipFree(n_S); hipFree(n_names); (void)hipGetLastError(); };
 #define UP_CHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { drop(); return set_err(e_ == hipErrorOutOfMemory ? WM_ENOMEM : WM_ENODEV, "%s failed: %s", #x, hipGetErrorString(e_)); } } while (0)
 	UP_CHK(hipMalloc((void**)&n_hkey, ix.hkey.size() * 8 + 8));
 	UP_CHK(hipMalloc((void**)&n_hval, ix.hval.size() * 8 + 8));
 	UP_CHK(hipMalloc((void**)&n_P, ix.P.size() * 8 + 8));
 	UP_CHK(hipMalloc((void**)&n_bloom, ix.bloom.bits.size() + 8));
 	UP_CHK(hipMalloc((void**)&n_S, ix.S.size() * 4 + 8));
+	const std::vector<uint32_t> names = name_tables(ix);      // derived from the contig names this process holds: nothing to receive
+	UP_CHK(hipMalloc((void**)&n_names, names.size() * 4 + 8));
+	UP_CHK(hipMemcpy(n_names, names.data(), names.size() * 4, hipMemcpyHostToDevice));
 	UP_CHK(hipMemcpy(n_S, ix.S.data(), ix.S.size() * 4, hipMemcpyHostToDevice));
 	UP_CHK(hipMemcpy(n_hkey, ix.hkey.data(), ix.hkey.size() * 8, hipMemcpyHostToDevice));
 	UP_CHK(hipMemcpy(n_hval, ix.hval.data(), ix.hval.size() * 8, hipMemcpyHostToDevice));
 	if (!ix.P.empty()) UP_CHK(hipMemcpy(n_P, ix.P.data(), ix.P.size() * 8, hipMemcpyHostToDevice));
 	UP_CHK(hipMemcpy(n_bloom, ix.bloom.bits.data(), ix.bloom.bits.size(), hipMemcpyHostToDevice));
 #undef UP_CHK
-	if (c->have_index && c->owns_index) { hipFree(c->d_hkey); hipFree(c->d_hval); hipFree(c->d_P); hipFree(c->d_bloom); hipFree(c->d_S); }
+	if (c->have_index && c->owns_index) { hipFree(c->d_hkey); hipFree(c->d_hval); hipFree(c->d_P); hipFree(c->d_bloom); hipFree(c->d_S); hipFree(c->d_name_rank); }
 	if (!c->have_index && c->owns_filter && c->d_bloom) hipFree(c->d_bloom);
 	c->owns_filter = false;
-	c->d_hkey = n_hkey; c->d_hval = n_hval; c->d_P = n_P; c->d_bloom = n_bloom; c->d_S = n_S;
+	c->d_hkey = n_hkey; c->d_hval = n_hval; c->d_P = n_P; c->d_bloom = n_bloom; c->d_S = n_S; c->d_name_rank = n_names; c->d_seq_len = n_names + ix.seq.size();
 	c->seq_off.clear(); c->seq_len.clear();
 	for (const wm::RefSeq &r : ix.seq) { c->seq_off.push_back(r.offset); c->seq_len.push_back(r.len); }
 	c->hbits = ix.hbits;
@@ -414,14 +433,17 @@ extern "C" int wm_index_upload_dev(wm_ctx_t *c, const wm_index_t *h, const void 
 	}
 	// new arrays first, the context's old index is released only when all of them are there and filled (a failed allocation used to leave
 	// the context without any index, and the arrays already allocated leaked)
-	uint64_t *n_hkey = 0, *n_hval = 0, *n_P = 0; uint8_t *n_bloom = 0; uint32_t *n_S = 0;
-	auto drop = [&]() { hipFree(n_hkey); hipFree(n_hval); hipFree(n_P); hipFree(n_bloom); hipFree(n_S); (void)hipGetLastError(); };
+	uint64_t *n_hkey = 0, *n_hval = 0, *n_P = 0; uint8_t *n_bloom = 0; uint32_t *n_S = 0, *n_names = 0;
+	auto drop = [&]() { hipFree(n_hkey); hipFree(n_hval); hipFree(n_P); hipFree(n_bloom); hipFree(n_S); hipFree(n_names); (void)hipGetLastError(); };
 #define UP_CHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { drop(); return set_err(e_ == hipErrorOutOfMemory ? WM_ENOMEM : WM_ENODEV, "%s failed: %s", #x, hipGetErrorString(e_)); } } while (0)
 	UP_CHK(hipMalloc((void**)&n_hkey, ix.hkey.size() * 8 + 8));
 	UP_CHK(hipMalloc((void**)&n_hval, ix.hval.size() * 8 + 8));
 	UP_CHK(hipMalloc((void**)&n_P, ix.P.size() * 8 + 8));
 	UP_CHK(hipMalloc((void**)&n_bloom, ix.bloom.bits.size() + 8));
 	UP_CHK(hipMalloc((void**)&n_S, ix.S.size() * 4 + 8));
+	const std::vector<uint32_t> names = name_tables(ix);      // derived from the contig names this process holds: nothing to receive
+	UP_CHK(hipMalloc((void**)&n_names, names.size() * 4 + 8));
+	UP_CHK(hipMemcpy(n_names, names.data(), names.size() * 4, hipMemcpyHostToDevice));
 	UP_CHK(hipMemcpyPeer(n_S, c->device, d_S, src_device, ix.S.size() * 4));
 	UP_CHK(hipMemcpyPeer(n_hkey, c->device, d_hkey, src_device, ix.hkey.size() * 8));
 	UP_CHK(hipMemcpyPeer(n_hval, c->device, d_hval, src_device, ix.hval.size() * 8));
@@ -429,10 +451,10 @@ extern "C" int wm_index_upload_dev(wm_ctx_t *c, const wm_index_t *h, const void 
 	UP_CHK(hipMemcpyPeer(n_bloom, c->device, d_bloom, src_device, ix.bloom.bits.size()));
 	UP_CHK(hipDeviceSynchronize());
 #undef UP_CHK
-	if (c->have_index && c->owns_index) { hipFree(c->d_hkey); hipFree(c->d_hval); hipFree(c->d_P); hipFree(c->d_bloom); hipFree(c->d_S); }
+	if (c->have_index && c->owns_index) { hipFree(c->d_hkey); hipFree(c->d_hval); hipFree(c->d_P); hipFree(c->d_bloom); hipFree(c->d_S); hipFree(c->d_name_rank); }
 	if (!c->have_index && c->owns_filter && c->d_bloom) hipFree(c->d_bloom);
 	c->owns_filter = false;
-	c->d_hkey = n_hkey; c->d_hval = n_hval; c->d_P = n_P; c->d_bloom = n_bloom; c->d_S = n_S;
+	c->d_hkey = n_hkey; c->d_hval = n_hval; c->d_P = n_P; c->d_bloom = n_bloom; c->d_S = n_S; c->d_name_rank = n_names; c->d_seq_len = n_names + ix.seq.size();
 	c->seq_off.clear(); c->seq_len.clear();
 	for (const wm::RefSeq &r : ix.seq) { c->seq_off.push_back(r.offset); c->seq_len.push_back(r.len); }
 	c->hbits = ix.hbits;
@@ -850,6 +872,12 @@ catch (const std::bad_alloc &) { return set_err(WM_ENOMEM, "out of host memory")
 
 extern "C" int wm_seed_batch(wm_ctx_t *c, int n, const wm128_t *mini, const uint64_t *mini_off, const int32_t *n_mini, const int32_t *qlen,
                              int max_occ, int64_t flag, wm128_t *out, size_t out_cap, uint64_t *out_off, int32_t *n_anchors, int32_t *rep_len)
+{
+	return wm_seed_batch_keyed(c, n, mini, mini_off, n_mini, qlen, 0, max_occ, flag, out, out_cap, out_off, n_anchors, rep_len);
+}
+
+extern "C" int wm_seed_batch_keyed(wm_ctx_t *c, int n, const wm128_t *mini, const uint64_t *mini_off, const int32_t *n_mini, const int32_t *qlen, const wm_qkey_t *keys,
+                                   int max_occ, int64_t flag, wm128_t *out, size_t out_cap, uint64_t *out_off, int32_t *n_anchors, int32_t *rep_len)
 try {
 	if (!c || !c->have_index) return set_err(WM_EINVAL, "wm_index_upload has not been called on this context");
 	if (n <= 0) return WM_OK;
@@ -872,7 +900,8 @@ try {
 		for (size_t t = 0; t < todo.size(); ++t) {
 			const int i = todo[t];
 			jb[t].mini_off = mini_off[i]; jb[t].n_mini = n_mini[i]; jb[t].qlen = qlen[i]; jb[t].max_occ = max_occ; jb[t].cap = want[i];
-			jb[t].flag = (int32_t)(flag & (0x100000 | 0x200000)); jb[t].pad = 0;
+			// the name bits travel only with a key (skip_seed with qname == NULL ignores them, src/map.c:135)
+			jb[t].flag = (int32_t)(flag & (0x100000 | 0x200000 | (keys && c->d_name_rank ? 3 : 0))); jb[t].q_lo = keys ? keys[i].lo : 0; jb[t].q_eq = keys ? (int32_t)keys[i].eq : 0; jb[t].pad = 0;
 			jb[t].out_off = tot; tot += want[i];
 			occ_off[t] = occ_tot; occ_tot += n_mini[i];
 		}
@@ -886,7 +915,7 @@ try {
 		HIPCHK(hipMemcpyAsync(d_jobs, jb.data(), jb.size() * sizeof(wm_seed_job_t), hipMemcpyHostToDevice, c->stream));
 		HIPCHK(hipMemcpyAsync(d_occ_off, occ_off.data(), jb.size() * 8, hipMemcpyHostToDevice, c->stream));
 		HIPCHK(hipMemcpyAsync(d_mini, mini, mini_total * sizeof(wm128_t), hipMemcpyHostToDevice, c->stream));
-		wm_index_view_t ix = { c->d_hkey, c->d_hval, c->d_P, c->hbits, 0 };
+		wm_index_view_t ix = { c->d_hkey, c->d_hval, c->d_P, c->hbits, 0, c->d_name_rank, c->d_seq_len };
 		HIPCHK(hipEventRecord(c->ev[0], c->stream));
 		hipLaunchKernelGGL(seed_kernel, dim3((int)jb.size()), dim3(64), 0, c->stream, ix, d_jobs, d_mini, d_out, d_occ, d_occ_off, d_res);
 		HIPCHK(hipEventRecord(c->ev[1], c->stream));

@@ -50,7 +50,9 @@ typedef struct {
 	uint64_t out_off;     // first anchor slot in the anchor pool
 	int32_t n_mini, qlen;
 	int32_t max_occ, cap; // occurrence cut-off (mid_occ); capacity of the anchor slot
-	int32_t flag, pad;    // MM_F_FOR_ONLY / MM_F_REV_ONLY bits
+	int32_t flag;         // MM_F_FOR_ONLY / MM_F_REV_ONLY bits; MM_F_NO_DIAG / MM_F_NO_DUAL (0x1 / 0x2) only together with a name key
+	uint32_t q_lo;        // name key of the query (skip_seed, src/map.c:132-154; host/wm_index.h): distinct contig names smaller than the query's name ...
+	int32_t q_eq, pad;    // ... and whether the name occurs among the contigs. All zero: no key (the two name bits must be clear)
 } wm_seed_job_t;
 
 typedef struct { int32_t n_anchors, rep_len; } wm_seed_res_t;
@@ -58,6 +60,7 @@ typedef struct { int32_t n_anchors, rep_len; } wm_seed_res_t;
 typedef struct {          // flat index view in HBM (host/wm_index.h)
 	const uint64_t *hkey, *hval, *P;
 	int32_t hbits, pad;
+	const uint32_t *name_rank, *seq_len;   // per contig: dense rank of its name among the distinct contig names (strcmp order), its length; read only by jobs with a name key
 } wm_index_view_t;
 
 // ---- chain DP fill (mm_chain_dp, src/chain.c:45-90) ----
@@ -73,10 +76,12 @@ typedef struct {
 	int64_t seq_off;      // first 0..4 code relative to the call's sequence base pointer (as wm_sketch_job_t::seq_off); < 0: no sequence, only handed-in anchors
 	uint64_t pre_off;     // first handed-in anchor in the call's `pre` pool
 	int32_t len, n_pre;
-	int32_t max_occ, seed_flag;                                                        // collect_seed_hits: mid_occ, MM_F_FOR_ONLY / MM_F_REV_ONLY bits
+	int32_t max_occ, seed_flag;                                                        // collect_seed_hits: mid_occ, MM_F_FOR_ONLY / MM_F_REV_ONLY bits (+ MM_F_NO_DIAG / MM_F_NO_DUAL with a name key)
 	int32_t max_dist_x, min_dist_x, max_dist_y, bw, max_skip, max_iter, min_cnt, min_sc;   // mm_chain_dp
 	float gap_scale;
 	int32_t is_cdna;
+	uint32_t q_lo;        // name key of the query, as wm_seed_job_t (read only when seed_flag carries 0x1 / 0x2)
+	int32_t q_eq;
 } wm_win_job_t;
 
 typedef struct {          // per job on the device: where its anchors live and what came out

@@ -71,6 +71,8 @@ struct GpuOpsCtx {
 		std::vector<int32_t> nm(n), ql(n), na(n), rl(n);
 		size_t tot = 0;
 		for (int i = 0; i < n; ++i) { moff[i] = tot; nm[i] = reqs[i]->n_mini; ql[i] = reqs[i]->qlen; tot += reqs[i]->n_mini; }
+		std::vector<wm_qkey_t> keys;                  // name keys (self / all-vs-all mapping): all requests of a call come from one mapper, so all or none carry one
+		if (reqs[0]->has_key) { keys.resize(n); for (int i = 0; i < n; ++i) keys[i] = { reqs[i]->q_lo, reqs[i]->q_eq }; }
 		UBuf<wm128_t> mini(tot + 1, c);
 		WM_SITE("seed.pack");
 		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) { memcpy(mini.data() + moff[i], reqs[i]->mini, (size_t)reqs[i]->n_mini * sizeof(wm128_t)); });
@@ -78,7 +80,7 @@ struct GpuOpsCtx {
 		for (int attempt = 0; attempt < 6; ++attempt) {
 			UBuf<wm128_t> out(cap, c);
 			const double ts = now_ms();
-			const int rc = wm_seed_batch(c, n, mini.data(), moff.data(), nm.data(), ql.data(), reqs[0]->max_occ, reqs[0]->flag, out.data(), out.size(), ooff.data(), na.data(), rl.data());
+			const int rc = wm_seed_batch_keyed(c, n, mini.data(), moff.data(), nm.data(), ql.data(), keys.empty() ? 0 : keys.data(), reqs[0]->max_occ, reqs[0]->flag, out.data(), out.size(), ooff.data(), na.data(), rl.data());
 			if (rc == WM_ENOMEM && strstr(wm_err_text(), "anchor output pool")) { cap *= 8; continue; }
 			if (rc) { fail("seed"); return; }
 			t_seed += now_ms() - ts;
@@ -129,6 +131,8 @@ struct GpuOpsCtx {
 			}
 		const double ts = now_ms();
 		UBuf<wm_window_job_t> jobs(n, c);
+		std::vector<wm_qkey_t> keys;              // name keys (self / all-vs-all mapping): all requests of a call come from one mapper, so all or none carry one
+		if (reqs[0]->has_key) { keys.resize(n); for (int i = 0; i < n; ++i) keys[i] = { reqs[i]->q_lo, reqs[i]->q_eq }; }
 		size_t stage = 0, npre = 0;
 		for (int i = 0; i < n; ++i) {
 			const wm::WindowReq &r = *reqs[i];
@@ -154,7 +158,7 @@ struct GpuOpsCtx {
 		for (int round = 0; round < 2; ++round) {
 			ArenaMark mark(c);
 			WinDev D;
-			int rc = window_launch(c, n, jobs.data(), seqs.data(), stage, pre.data(), npre, reqs[0]->max_occ, reqs[0]->flag, round == 1, D);
+			int rc = window_launch(c, n, jobs.data(), seqs.data(), stage, pre.data(), npre, reqs[0]->max_occ, reqs[0]->flag, round == 1, D, keys.empty() ? 0 : keys.data());
 			if (!rc) rc = window_verdict(D, round);
 			if (rc < 0) { fail("window"); return; }
 			if (rc == 1) continue;
@@ -554,7 +558,7 @@ extern "C" int wm_mapper_set_threads(wm_mapper_t *m, int n_threads, size_t arena
 		const int rc = wm_ctx_create(m->c->device, arena_bytes_per_context ? arena_bytes_per_context : m->c->arena_bytes, &w);
 		if (rc) return rc;
 		w->d_hkey = m->c->d_hkey; w->d_hval = m->c->d_hval; w->d_P = m->c->d_P; w->d_bloom = m->c->d_bloom; w->hbits = m->c->hbits; w->skp = m->c->skp;
-		w->d_S = m->c->d_S; w->seq_off = m->c->seq_off; w->seq_len = m->c->seq_len;
+		w->d_S = m->c->d_S; w->d_name_rank = m->c->d_name_rank; w->d_seq_len = m->c->d_seq_len; w->seq_off = m->c->seq_off; w->seq_len = m->c->seq_len;
 		w->have_index = true; w->owns_index = false;
 		w->host_threads = m->c->host_threads;
 		m->workers.push_back(w);

@@ -103,6 +103,7 @@ struct wm_ctx_s {
 	uint8_t *d_bloom;
 	uint32_t *d_S;                              // packed reference (4 bits per base), for position jobs
 	std::vector<uint64_t> seq_off; std::vector<uint32_t> seq_len;       // contig table of the uploaded index (bounds of position jobs)
+	uint32_t *d_name_rank, *d_seq_len;          // per contig: rank of its name (host/wm_index.h NameTable) and its length, one allocation: what skip_seed (src/map.c:132-154) compares on the device
 	// the read codes of the current mini-batch(es), resident: 2 bits per base in d_reads, the ambiguity bitmap in d_reads_nm (reads2bit.h; one allocation);
 	// reads_bytes = bases a job may address, reads_cap = bases the allocation holds (wm_reads_upload / GpuOps::load_reads)
 	uint64_t *d_reads, *d_reads_nm; size_t reads_bytes, reads_cap; bool owns_reads;
@@ -138,6 +139,6 @@ int sketch_launch(wm_ctx_t *c, int n, const wm_sketch_job_t *h_jobs, const wm_sk
 // wm_window.hip
 struct WinDev { wm_win_res_t *d_res; uint64_t *d_upool; wm128_t *d_vpool; uint64_t *d_ctr; uint64_t ctr[4]; uint32_t tot[3]; };
 int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
-                  int max_occ, int64_t flag, bool slot_full, WinDev &D);
+                  int max_occ, int64_t flag, bool slot_full, WinDev &D, const wm_qkey_t *keys = 0);
 int window_fetch(wm_ctx_t *c, const WinDev &D, int n, wm_window_res_t *res, uint64_t *u_pool, wm128_t *a_pool);
 int window_verdict(const WinDev &D, int round);

@@ -155,7 +155,7 @@ extern "C" int wm_ctx_create(int device, size_t arena_bytes, wm_ctx_t **out)
 	c->owns_filter = false;
 	c->pin_small = 0;
 	if (hipHostMalloc((void**)&c->pin_small, 256, hipHostMallocDefault) != hipSuccess) { c->pin_small = 0; (void)hipGetLastError(); }
-	c->d_S = 0; c->d_reads = 0; c->d_reads_nm = 0; c->reads_bytes = c->reads_cap = 0; c->owns_reads = false;
+	c->d_S = 0; c->d_name_rank = c->d_seq_len = 0; c->d_reads = 0; c->d_reads_nm = 0; c->reads_bytes = c->reads_cap = 0; c->owns_reads = false;
 	*out = c;
 	return WM_OK;
 }
@@ -175,7 +175,7 @@ extern "C" void wm_ctx_destroy(wm_ctx_t *c)
 	for (int i = 0; i < 5; ++i) hipEventDestroy(c->kev[i]);
 	for (int k = 0; k < WM_KSW_NCLASS; ++k) { hipEventDestroy(c->cev[k][0]); hipEventDestroy(c->cev[k][1]); }
 	hipFree(c->arena);
-	if (c->have_index && c->owns_index) { hipFree(c->d_hkey); hipFree(c->d_hval); hipFree(c->d_P); hipFree(c->d_bloom); hipFree(c->d_S); }
+	if (c->have_index && c->owns_index) { hipFree(c->d_hkey); hipFree(c->d_hval); hipFree(c->d_P); hipFree(c->d_bloom); hipFree(c->d_S); hipFree(c->d_name_rank); }
 	if (c->d_reads && c->owns_reads) hipFree(c->d_reads);
 	if (!c->have_index && c->owns_filter && c->d_bloom) hipFree(c->d_bloom);
 	delete c;

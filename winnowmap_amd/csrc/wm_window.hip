@@ -201,7 +201,7 @@ __global__ __launch_bounds__(64) void win_extract_kernel(const wm_win_job_t *__r
 
 // device side of one call: everything up to the dense result pools; the caller copies them out. slot_full: full-size minimizer slots (retry)
 int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
-                         int max_occ, int64_t flag, bool slot_full, WinDev &D)
+                         int max_occ, int64_t flag, bool slot_full, WinDev &D, const wm_qkey_t *keys)
 {
 	const int w = c->skp.w;
 	(void)w;
@@ -218,7 +218,9 @@ int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t
 		if (s.len < 0 || s.n_pre < 0 || (s.n_pre > 0 && s.pre_off + (uint64_t)s.n_pre > n_pre_total) || s.seq_off < -2 ||
 		    (s.seq_off >= 0 && (!c->d_reads || (uint64_t)s.seq_off + (uint64_t)s.len > c->reads_bytes)) ||
 		    (s.seq_off == -1 && s.stage_off + (uint64_t)s.len > seqs_bytes)) { if (bad < 0) bad = i; }
-		d.seq_off = has_seq ? 0 : -1; d.pre_off = s.pre_off; d.len = s.len; d.n_pre = s.n_pre; d.max_occ = max_occ; d.seed_flag = (int32_t)(flag & (0x100000 | 0x200000));
+		d.seq_off = has_seq ? 0 : -1; d.pre_off = s.pre_off; d.len = s.len; d.n_pre = s.n_pre; d.max_occ = max_occ;
+		// (the name bits travel only with a key: skip_seed with qname == NULL ignores them, src/map.c:135)
+		d.seed_flag = (int32_t)(flag & (0x100000 | 0x200000 | (keys && c->d_name_rank ? 3 : 0))); d.q_lo = keys ? keys[i].lo : 0; d.q_eq = keys ? (int32_t)keys[i].eq : 0;
 		d.max_dist_x = s.par.max_dist_x; d.min_dist_x = s.par.min_dist_x; d.max_dist_y = s.par.max_dist_y; d.bw = s.par.bw; d.max_skip = s.par.max_skip; d.max_iter = s.par.max_iter;
 		d.min_cnt = s.par.min_cnt; d.min_sc = s.par.min_sc; d.gap_scale = s.par.gap_scale; d.is_cdna = s.par.is_cdna != 0;
 		wm_sketch_job_t &k = sj[i];
@@ -284,7 +286,7 @@ int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t
 	if (d_tie) HIPCHK(hipMemsetAsync(d_tie, 0, 32, c->stream));
 	HIPCHK(hipEventRecord(c->ev[0], c->stream));
 	if (const int rc = sketch_launch(c, n, sj.data(), d_sj, d_ord, d_seqs, d_so, d_sx, d_sy, d_sl, d_mini, d_mcnt, !slot_full, d_long, long_bytes)) return rc;
-	wm_index_view_t ix = { c->d_hkey, c->d_hval, c->d_P, c->hbits, 0 };
+	wm_index_view_t ix = { c->d_hkey, c->d_hval, c->d_P, c->hbits, 0, c->d_name_rank, c->d_seq_len };
 	hipLaunchKernelGGL(win_seed_kernel, dim3(n), dim3(64), 0, c->stream, ix, d_jobs, d_sj, d_mcnt, d_mini, d_pre, d_occ, d_first, d_emit, d_a, d_ctr, cap, D.d_res, (int*)(d_ctr + 3));
 	const size_t ws_bytes = (size_t)wmk::WIN_WS_PAD * 4;
 	static const int kSmall = wmk::WIN_SMALL, kLarge = 4096;
@@ -390,6 +392,12 @@ int window_verdict(const WinDev &D, int round)
 
 extern "C" int wm_window_batch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
                                int max_occ, int64_t flag, wm_window_res_t *res, uint64_t *u_pool, size_t u_cap, size_t *u_used, wm128_t *a_pool, size_t a_cap, size_t *a_used)
+{
+	return wm_window_batch_keyed(c, n, jobs, 0, seqs, seqs_bytes, pre, n_pre_total, max_occ, flag, res, u_pool, u_cap, u_used, a_pool, a_cap, a_used);
+}
+
+extern "C" int wm_window_batch_keyed(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const wm_qkey_t *keys, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
+                                     int max_occ, int64_t flag, wm_window_res_t *res, uint64_t *u_pool, size_t u_cap, size_t *u_used, wm128_t *a_pool, size_t a_cap, size_t *a_used)
 try {
 	if (u_used) *u_used = 0;
 	if (a_used) *a_used = 0;
@@ -401,7 +409,7 @@ try {
 	for (int round = 0; round < 2; ++round) {
 		ArenaMark mark(c);
 		WinDev D;
-		int rc = window_launch(c, n, jobs, seqs, seqs_bytes, pre, n_pre_total, max_occ, flag, round == 1, D);
+		int rc = window_launch(c, n, jobs, seqs, seqs_bytes, pre, n_pre_total, max_occ, flag, round == 1, D, keys);
 		if (rc) return rc;
 		rc = window_verdict(D, round);
 		if (rc < 0) return rc;

@@ -136,6 +136,39 @@ class Context:
         _chk(lib().wm_ksw_batch_pos_zd(self._h, C.byref(score), len(jobs), jobs.ctypes.data, res.ctypes.data, pool.ctypes.data, cap, C.byref(used), zd.ctypes.data))
         return res, pool[:used.value], zd
 
+    def seed_batch_keyed(self, mini, mini_off, n_mini, qlen, keys, max_occ, flag, out_cap):
+        """wm_seed_batch_keyed: collect_seed_hits with skip_seed's name comparison (src/map.c:132-154). mini: uint64 [n_total, 2]; keys: uint32 [n, 2]
+        from Index.query_keys (None = wm_seed_batch: MM_F_NO_DIAG / MM_F_NO_DUAL are ignored). Returns (anchors uint64 [out_cap, 2], out_off, n_anchors, rep_len)."""
+        L = lib()
+        L.wm_seed_batch_keyed.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_int64, C.c_void_p, C.c_size_t] + [C.c_void_p] * 3
+        n = len(n_mini)
+        mini = np.ascontiguousarray(mini, np.uint64)
+        mini_off, n_mini, qlen = np.ascontiguousarray(mini_off, np.uint64), np.ascontiguousarray(n_mini, np.int32), np.ascontiguousarray(qlen, np.int32)
+        keys = None if keys is None else np.ascontiguousarray(keys, np.uint32).reshape(n, 2)
+        out = np.zeros((out_cap, 2), np.uint64)
+        out_off, n_a, rep_len = np.zeros(n, np.uint64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        _chk(L.wm_seed_batch_keyed(self._h, n, mini.ctypes.data, mini_off.ctypes.data, n_mini.ctypes.data, qlen.ctypes.data, None if keys is None else keys.ctypes.data,
+                                   max_occ, flag, out.ctypes.data, out_cap, out_off.ctypes.data, n_a.ctypes.data, rep_len.ctypes.data))
+        return out, out_off, n_a, rep_len
+
+    def window_batch_keyed(self, jobs, keys, seqs, pre, max_occ, flag, u_cap, a_cap):
+        """wm_window_batch_keyed. jobs: structured array WINDOW_JOB; keys: uint32 [n, 2] or None (= wm_window_batch); seqs: uint8 staging codes; pre: uint64 [n_pre, 2].
+        Returns (res WINDOW_RES [n], u_pool, a_pool [.., 2])."""
+        L = lib()
+        L.wm_window_batch_keyed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        n = len(jobs)
+        jobs = np.ascontiguousarray(jobs, WINDOW_JOB)
+        keys = None if keys is None else np.ascontiguousarray(keys, np.uint32).reshape(n, 2)
+        seqs = np.ascontiguousarray(seqs, np.uint8)
+        pre = np.ascontiguousarray(pre, np.uint64).reshape(-1, 2)
+        res = np.zeros(n, WINDOW_RES)
+        u_pool, a_pool = np.zeros(u_cap + 1, np.uint64), np.zeros((a_cap + 1, 2), np.uint64)
+        uu, au = C.c_size_t(), C.c_size_t()
+        _chk(L.wm_window_batch_keyed(self._h, n, jobs.ctypes.data, None if keys is None else keys.ctypes.data, seqs.ctypes.data, seqs.nbytes, pre.ctypes.data, len(pre),
+                                     max_occ, flag, res.ctypes.data, u_pool.ctypes.data, u_cap, C.byref(uu), a_pool.ctypes.data, a_cap, C.byref(au)))
+        return res, u_pool[:uu.value], a_pool[:au.value]
+
     def ksw_prepare(self, score, jobs, seqs):
         jobs = np.ascontiguousarray(jobs, KSW_JOB_DTYPE)
         seqs = np.ascontiguousarray(seqs, np.uint8)
@@ -231,6 +264,13 @@ def pack_jobs(pairs, w=751, zdrop=400, end_bonus=-1, flag=0):
 
 
 # ---- index + mapper ------------------------------------------------------------------------------------
+# wm_window_job_t / wm_window_res_t of include/wm_gpu.h
+WINDOW_JOB = np.dtype([("seq_off", "<i8"), ("stage_off", "<u8"), ("pre_off", "<u8"), ("len", "<i4"), ("n_pre", "<i4"),
+                       ("max_dist_x", "<i4"), ("min_dist_x", "<i4"), ("max_dist_y", "<i4"), ("bw", "<i4"), ("max_skip", "<i4"), ("max_iter", "<i4"), ("min_cnt", "<i4"), ("min_sc", "<i4"),
+                       ("gap_scale", "<f4"), ("is_cdna", "<i4")])
+WINDOW_RES = np.dtype([("n_anchors", "<i4"), ("rep_len", "<i4"), ("n_mini", "<i4"), ("n_u", "<i4"), ("n_v", "<i4"), ("u_off", "<u4"), ("a_off", "<u4")])
+
+
 def _bind_map(L):
     if getattr(L, "_wm_map_bound", False):
         return
@@ -470,6 +510,19 @@ class Index:
         L = lib()
         return [L.wm_index_seq_name(self._h, i).decode() for i in range(L.wm_index_n_seq(self._h))]
 
+    def query_key(self, name):
+        """(lo, eq) of a query name for THIS index: lo = distinct contig names that are strcmp-smaller, eq = the name is a contig's. What the device compares
+        instead of skip_seed's strcmp(qname, contig name) (src/map.c:132-154) in self / all-vs-all mapping; wm_index_query_key."""
+        return tuple(int(x) for x in self.query_keys([name])[0])
+
+    def query_keys(self, names):
+        L = lib()
+        L.wm_index_query_key.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
+        out = np.zeros((len(names), 2), np.uint32)
+        for i, nm in enumerate(names):
+            _chk(L.wm_index_query_key(self._h, nm if isinstance(nm, bytes) else nm.encode(), out[i:].ctypes.data))
+        return out
+
     def close(self):
         if self._h:
             lib().wm_index_destroy(self._h)
@@ -477,6 +530,9 @@ class Index:
 
 
 MM_F_CIGAR, MM_F_OUT_SAM, MM_F_OUT_CG = 0x4, 0x8, 0x20
+# self / all-vs-all mapping (src/minimap.h:9-31, skip_seed src/map.c:132-154): -D, --dual=no, -P, --no-long-join; -X is all four (src/main.c)
+MM_F_NO_DIAG, MM_F_NO_DUAL, MM_F_NO_LJOIN, MM_F_ALL_CHAINS = 0x1, 0x2, 0x400, 0x800000
+MM_F_AVA = MM_F_ALL_CHAINS | MM_F_NO_DIAG | MM_F_NO_DUAL | MM_F_NO_LJOIN
 STAT_NAMES = ("super_steps", "ksw_jobs", "chain_jobs", "seed_jobs", "sketch_jobs", "dp_cells", "ksw_kernel_us", "aux_kernel_us", "read_bases")
 
 
