@@ -427,6 +427,9 @@ int wm_mapper_stats(const wm_mapper_t *m, uint64_t *out9);
  * out[3k+2] = launches. cap = doubles available in out; *n_classes receives the class count. Feeds bench.py's roofline. */
 int wm_mapper_kernel_stats(const wm_mapper_t *m, double *out, int cap, int *n_classes);
 int wm_ksw_n_classes(void);      /* the class count (what out of wm_mapper_kernel_stats / _union must hold) */
+/* the same table for ONE context, from its own counters since wm_ctx_create (a context used without a mapper: wm_ksw_batch and its kin). The counters
+ * fill only while the class events are on (the default; WM_KSW_CLASS_EVENTS=0 turns them off). */
+int wm_ctx_kernel_stats(const wm_ctx_t *ctx, double *out, int cap, int *n_classes);
 /* Launches of one class overlap on different streams, so the summed durations above are residency. out[k] = ms during which AT LEAST ONE launch of
  * class k was running (union of the launch intervals on the device clock) after since_ms; *now_ms = the clock now (the next call's since_ms). */
 int wm_mapper_kernel_union(const wm_mapper_t *m, double since_ms, double *out, int cap, double *now_ms);

@@ -195,3 +195,116 @@ def dual_pairs(seed, n, ncs=(4, 8, 16)):
         if jobs:
             out.append((nc, sc, jobs))
     return out
+
+
+# ---- the sizes and scores at which the ksw routing changes hands (winnowmap_amd/csrc/ksw_plan.h) ------------------------------------------------
+# (a,b,q,e,q2,e2): map-ont; asm5 (the reference's int8 lanes wrap); asm10; two sets ON the limit (q+e)+(q2+e2) == 127 of mm_check_opt (src/options.c:166-176);
+# a large match score
+SCORING_EDGE = [(2, 4, 4, 2, 24, 1), (1, 19, 39, 3, 81, 1), (1, 9, 16, 2, 41, 1), (1, 4, 40, 4, 80, 3), (6, 2, 5, 3, 10, 1), (1, 30, 60, 3, 62, 2)]
+# the traceback pitches n_col at which wm_ksw_classify (496, 1008, 2032, 4080, 8176) and wm_ksw_route (768, 1792, 3584, 3840, 7168) switch kernel
+CLASS_EDGES = (496, 768, 1008, 1792, 2032, 3584, 3840, 4080, 7168, 8176)
+EDGE_FLAGS = (0x08, 0x40, 0x00, 0xC2, 0x42)
+
+
+def _edge_query(t, ql, rng, tail):
+    """a query of exactly ql bases: the target's prefix at 3-4 % divergence (tail: only 35-55 % of it), then unrelated bases"""
+    n = min(len(t), ql)
+    if tail:
+        n = max(1, int(n * rng.uniform(0.35, 0.55)))
+    q = synth.mutate_codes(t[:n], rng, 0.015, 0.01, 0.01)[:ql]
+    return np.concatenate([q, rng.integers(0, 4, ql - len(q)).astype(np.uint8)])
+
+
+def class_edge_cases(seed, edges, scoring=SCORING_EDGE[0]):
+    """Jobs right below and right above a class edge. With the limiter n = min(qlen, tlen, w + 1), wm_ksw_ncol gives n_col == E for n = E - 31 .. E - 16
+    and n_col == E + 16 from n = E - 15 on: per edge E, n = E - 31, E - 16 (the class below) and E - 15 (the class above), the limiter in turn tlen (query
+    longer), qlen (target longer) and w + 1 (both longer by 40 .. 300: the band clips); a related query and one that runs off (z-drop); one job with an N.
+    Edge 768 separates two stripe geometries, which only jobs of 4096 rows and more reach by default: two such jobs. From 3584 on (13 .. 67 M cells per
+    job) only n = E - 16 and E - 15, as an unbanded gap fill limited by tlen and as an extension limited by w + 1 whose query runs off.
+    Every job carries `n_col` and `edge`."""
+    a, b, q_, e, q2, e2 = scoring
+    rng = np.random.default_rng(seed)
+    out = []
+
+    def add(E, ql, tl, w, tail, flag=None, zdrop=None, end_bonus=None, n_at=None):
+        it = len(out)
+        t = rng.integers(0, 4, tl).astype(np.uint8)
+        q = _edge_query(t, ql, rng, tail)
+        if n_at is not None:
+            (q if it % 2 else t)[int(n_at)] = 4
+        ww = max(ql, tl) if w < 0 else w
+        n = min(ql, tl, ww + 1)
+        out.append(dict(q=q, t=t, a=a, b=b, q_=q_, e=e, q2=q2, e2=e2, w=w, zdrop=(400, 200, 100, -1)[it % 4] if zdrop is None else zdrop,
+                        end_bonus=(-1, 0, 10)[it % 3] if end_bonus is None else end_bonus, flag=EDGE_FLAGS[it % 5] if flag is None else flag,
+                        n_col=((n + 15) // 16 + 1) * 16, edge=E))
+
+    def sized(n, lim):
+        """(qlen, tlen, w) whose limiter `lim` (0 = tlen, 1 = qlen, 2 = w + 1) is n"""
+        d1, d2 = int(rng.integers(40, 301)), int(rng.integers(40, 301))
+        if lim == 2:
+            return n + d1, n + d2, n - 1
+        w = (-1, n + d1 + d2, n + d1 // 2)[len(out) % 3]                  # never the limiter; clips the longer operand or not
+        return (n + d1, n, w) if lim == 0 else (n, n + d1, w)
+
+    for E in edges:
+        if E >= 3584:
+            for n in (E - 16, E - 15):
+                add(E, n + int(rng.integers(40, 301)), n, -1, False, flag=0x08, zdrop=400, end_bonus=-1)
+                add(E, n + int(rng.integers(40, 301)), n + int(rng.integers(40, 301)), n - 1, True, flag=0x40, zdrop=(400, 200)[n & 1], end_bonus=(-1, 10)[n & 1])
+            continue
+        for n in (E - 31, E - 16, E - 15):
+            for lim in (0, 1, 2):
+                for tail in (False, True):
+                    add(E, *sized(n, lim), tail)
+        ql, tl, w = sized(E - 16, E // 16 % 3)
+        add(E, ql, tl, w, False, n_at=rng.integers(0, min(ql, tl)))
+        if E == 768:
+            for n in (E - 16, E - 15):
+                add(E, 4097 - n + int(rng.integers(0, 200)), n, -1, n & 1 == 0, flag=(0x08, 0x40)[n & 1])
+    return out
+
+
+STRIPE_FLAGS = (0x08, 0x08, 0x00, 0x40, 0xC2, 0x42, 0x80, 0x0A, 0x88)      # the nine of stripe_cases
+
+
+def chain_stripe_edge_cases(seed, sw, scoring=None):
+    """The ends of a job as the chained-workgroup kernel sees them (ksw_chain_kernel.h: stripes of sw = 256 / 512 target lanes, one wavefront each): tlen at
+    sw - 1 .. 3 sw + 1 (the wavefront count changes at every multiple of sw), a query half as long / as long / a stripe longer, bands inside one stripe, of
+    one stripe, and none. 7 x 3 x 5 = 105 small jobs; scoring: one SCORING_EDGE set, or None = in turn per case."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for tl in (sw - 1, sw, sw + 1, 2 * sw - 1, 2 * sw, 2 * sw + 1, 3 * sw + 1):
+        for qsel in range(3):
+            for w in (5, sw // 2, sw - 1, sw, -1):
+                it = len(out)
+                ql = (tl // 2 + int(rng.integers(-3, 4)), tl + int(rng.integers(-3, 4)), tl + sw + 9)[qsel]
+                t = rng.integers(0, 4, tl).astype(np.uint8)
+                q = rng.integers(0, 4, ql).astype(np.uint8) if it % 7 == 6 else _edge_query(t, ql, rng, it % 4 == 1)
+                if it % 13 == 5:
+                    q[int(rng.integers(0, ql))] = 4
+                if it % 17 == 9:
+                    t[int(rng.integers(0, tl))] = 4
+                a, b, q_, e, q2, e2 = SCORING_EDGE[it % len(SCORING_EDGE)] if scoring is None else scoring
+                out.append(dict(q=q, t=t, a=a, b=b, q_=q_, e=e, q2=q2, e2=e2, w=w, zdrop=(400, 200, 100, -1, 50)[it % 5], end_bonus=(-1, 0, 10)[it % 3],
+                                flag=STRIPE_FLAGS[it % 9]))
+    return out
+
+
+def row_threshold_cases(seed, scoring=SCORING_EDGE[0]):
+    """qlen + tlen - 1 = 4095, 4096, 4097 rows under a band of 600 (n_col = 624: the 8-pair register class): either side of the 4096 rows from which such a job
+    leaves its one wavefront for a stripe / chained class (WM_KSW_STRIPE_ROWS8), at 2.5 M cells a job. Every job carries `rows`."""
+    a, b, q_, e, q2, e2 = scoring
+    rng = np.random.default_rng(seed)
+    out = []
+    for rows in (4095, 4096, 4097):
+        for k in range(6):
+            ql = (rows + 1) // 2 + (0, 290, -290)[k % 3] + int(rng.integers(-5, 6))
+            tl = rows + 1 - ql
+            t = rng.integers(0, 4, tl).astype(np.uint8)
+            q = _edge_query(t, ql, rng, k >= 3)
+            if k == 2:
+                q[int(rng.integers(0, ql))] = 4
+            it = len(out)
+            out.append(dict(q=q, t=t, a=a, b=b, q_=q_, e=e, q2=q2, e2=e2, w=600, zdrop=(400, 200, 100, -1)[it % 4], end_bonus=(-1, 0, 10)[it % 3],
+                            flag=EDGE_FLAGS[it % 5], rows=rows))
+    return out

@@ -647,3 +647,51 @@ def _chain_run(E, cases, forces):
             assert [int(x) for x in ez] == [o[k] for k in W.EZ_FIELDS], (force, klass, len(c["q"]), len(c["t"]), c["w"], hex(c["flag"]), c["zdrop"])
             assert np.array_equal(cig, o["cigar"]), (force, klass, len(c["q"]), len(c["t"]), c["w"], hex(c["flag"]), c["zdrop"])
     return n_run
+
+
+CHAIN_FORCES = [400 + g * 10 + v for g in (1, 2) for v in (0, 2, 3)]      # 256- and 512-lane stripes x (lean, CLIP, CLIP + HASN)
+
+
+def _chain_inputs(group):
+    """[(cases, forces)], runs at least — a job runs on the instantiations that serve it: CLIP + HASN always, CLIP unless it holds an N, the lean one when
+    its band never clips"""
+    if group == "random":              # the stripe kernel's small random cases: every flag / band / scoring combination
+        return [(kswcases.stripe_edge_cases(1, 150, 700) + kswcases.stripe_cases(2, 40, 700), CHAIN_FORCES)], 700
+    if group == "stripe_ends":         # tlen, qlen and the band at the stripe ends, the scoring sets up to the limit (q+e)+(q2+e2) == 127 in turn. Each on the geometry
+        # whose stripe ends it sits on: on the other one, 512 is what 2 x 256 already is, and 256 lies inside a stripe
+        return [(kswcases.chain_stripe_edge_cases(3, 256), CHAIN_FORCES[:3]), (kswcases.chain_stripe_edge_cases(4, 512), CHAIN_FORCES[3:])], 400
+    edge = [c for c in kswcases.class_edge_cases(5, (496, 768, 1008)) if len(c["q"]) + len(c["t"]) - 1 < 4096]
+    assert len(edge) == 3 * 19         # (without the two 4096-row jobs of edge 768, 3 M cells each: the GPU tests run them)
+    return [(edge, CHAIN_FORCES)], 250
+
+
+@pytest.mark.parametrize("group", ["random", "stripe_ends", "class_edges"])
+def test_chained_workgroup_ksw_kernel_matches_oracle(group):
+    """ksw_dp_chain: every wavefront of a job a workgroup of its own, rows handed to the right neighbour through a mailbox in global memory. The host's thread
+    scheduler supplies the interleavings; every rare path must have run, in every group of inputs."""
+    E = _load_chain()
+    ev0 = _chain_events(E)
+    inputs, at_least = _chain_inputs(group)
+    n_run = collections.Counter()
+    for cases, forces in inputs:
+        n_run += _chain_run(E, cases, forces)
+    ev = {k: v - ev0[k] for k, v in _chain_events(E).items()}
+    print("chain emulator, %s: runs %s, events %s" % (group, dict(n_run), ev))
+    assert sum(n_run.values()) >= at_least and min(n_run[1], n_run[2]) >= at_least // 4, n_run
+    for k in CHAIN_EVENTS:
+        assert ev[k] > 0, ev
+
+
+def test_chained_workgroup_ksw_kernel_with_late_consumers():
+    """the wavefronts of a job start 200 us apart, in ticket order (emu_chain_start_skew): a producer has filled its mailbox and waits (back-pressure)
+    before its consumer exists, as in a launch larger than the chip. Same results."""
+    E = _load_chain()
+    E.emu_chain_start_skew(200)
+    try:
+        cases = kswcases.chain_stripe_edge_cases(6, 256)[::3] + kswcases.stripe_cases(7, 12, 700) + kswcases.class_edge_cases(8, (768,))[:6]
+        n_run = _chain_run(E, cases, [413, 423])
+        n_run += _chain_run(E, cases[::4], [410, 412, 420, 422])
+    finally:
+        E.emu_chain_start_skew(0)
+    print("chain emulator, late consumers: runs %s" % dict(n_run))
+    assert n_run[1] >= 55 and n_run[2] >= 55, n_run

@@ -71,6 +71,51 @@ def test_ksw_vs_reference():
         assert all(o[k] == r[k] for k in W.EZ_FIELDS) and np.array_equal(o["cigar"], r["cigar"])
 
 
+def _oracle_equals_reference(cases):
+    """oracle == reference on every job: the ten ez fields and the CIGAR (eight jobs at a time: ctypes releases the GIL)"""
+    from concurrent.futures import ThreadPoolExecutor
+
+    def one(c):
+        kw = dict(mat=W.simple_mat(c["a"], c["b"], 1), q=c["q_"], e=c["e"], q2=c["q2"], e2=c["e2"], w=c["w"], zdrop=c["zdrop"], end_bonus=c["end_bonus"], flag=c["flag"])
+        o, r = W.o_ksw_extd2(c["q"], c["t"], **kw), W.r_ksw_extd2(c["q"], c["t"], **kw)
+        return all(o[k] == r[k] for k in W.EZ_FIELDS) and np.array_equal(o["cigar"], r["cigar"]), o
+    one(cases[0])                          # (loads both libraries; the reference chooses its SIMD build on the first call)
+    with ThreadPoolExecutor(8) as ex:
+        res = list(ex.map(one, cases))
+    bad = [(i, len(c["q"]), len(c["t"]), c["w"], hex(c["flag"]), c["zdrop"], (c["a"], c["b"], c["q_"], c["e"], c["q2"], c["e2"])) for i, (c, (ok, o)) in enumerate(zip(cases, res)) if not ok]
+    assert not bad, bad[:3]
+    return [o for ok, o in res]
+
+
+@pytest.mark.parametrize("si", range(len(kswcases.SCORING_EDGE)))
+def test_ksw_vs_reference_at_the_class_edges(si):
+    """what the GPU tests of hulls up to 8 192 lanes expect (tests/test_ksw_edges_gpu.py) is the oracle's word: the same jobs — either side of every class
+    edge of ksw_plan.h, under the scoring sets up to the limit of mm_check_opt and with asm5's wrapping int8 lanes — against the reference itself. The edges
+    up to 4080 under every set, 7168 and 8176 (50 .. 67 M cells a job) under the first two."""
+    _need_ref()
+    edges = [E for E in kswcases.CLASS_EDGES if E <= 4080 or si < 2]
+    out = _oracle_equals_reference(kswcases.class_edge_cases(40 + si, edges, kswcases.SCORING_EDGE[si]))
+    n_zd = sum(o["zdropped"] for o in out)
+    print("scoring set %d: %d jobs, %d z-dropped" % (si, len(out), n_zd))
+    a, b = kswcases.SCORING_EDGE[si][:2]
+    assert n_zd >= 5 or a >= 3 * b          # queries that run off do stop extensions (unless unrelated bases score above zero: a / 4 - 3 b / 4)
+
+
+def test_ksw_vs_reference_at_the_stripe_ends_of_the_chained_kernel():
+    _need_ref()
+    _oracle_equals_reference(kswcases.chain_stripe_edge_cases(3, 256))
+
+
+def test_ksw_vs_reference_when_a_mismatch_can_never_be_seen():
+    """src/ksw2_extd2_sse.c:92: with -min(mat) > 2 * (q + e) the reference returns before it does anything (ez as ksw_reset_extz left it, no CIGAR) —
+    the `never` branch of ksw_prepare_impl (wm_ksw.hip)"""
+    _need_ref()
+    sc = (1, 30, 4, 2, 24, 1)
+    cases = kswcases.class_edge_cases(7, (496,), sc) + kswcases.chain_stripe_edge_cases(8, 256, sc)[::5]
+    for o in _oracle_equals_reference(cases):
+        assert len(o["cigar"]) == 0 and o["score"] == -0x40000000 and o["max"] == 0 and o["max_q"] == -1 and o["reach_end"] == 0, o
+
+
 def test_extz2_equals_extd2_with_equal_pieces():
     _need_ref()
     import ctypes as C

@@ -183,6 +183,16 @@ extern "C" void wm_ctx_destroy(wm_ctx_t *c)
 
 extern "C" float wm_last_kernel_ms(const wm_ctx_t *c) { return c ? c->last_ms : 0.f; }
 extern "C" int wm_ctx_device(const wm_ctx_t *c) { return c ? c->device : -1; }
+// per ksw kernel class (ksw_plan.h) since the context was created, from the context's own counters: the layout of wm_mapper_kernel_stats
+// (wm_mapper.hip) — out[3*k] = summed launch durations in ms, out[3*k+1] = DP cells, out[3*k+2] = launches
+extern "C" int wm_ctx_kernel_stats(const wm_ctx_t *c, double *out, int cap, int *n_classes)
+{
+	if (n_classes) *n_classes = WM_KSW_NCLASS;
+	if (!c || !out) return set_err(WM_EINVAL, "null context or output");
+	if (cap < 3 * WM_KSW_NCLASS) return set_err(WM_EINVAL, "need room for %d doubles", 3 * WM_KSW_NCLASS);
+	for (int k = 0; k < WM_KSW_NCLASS; ++k) { out[3 * k] = c->k_ms[k]; out[3 * k + 1] = (double)c->k_cells[k]; out[3 * k + 2] = (double)c->k_launches[k]; }
+	return WM_OK;
+}
 
 void *arena_take(wm_ctx_t *c, size_t bytes)
 {

@@ -169,6 +169,16 @@ class Context:
                                      max_occ, flag, res.ctypes.data, u_pool.ctypes.data, u_cap, C.byref(uu), a_pool.ctypes.data, a_cap, C.byref(au)))
         return res, u_pool[:uu.value], a_pool[:au.value]
 
+    def kernel_stats(self):
+        """wm_ctx_kernel_stats: {class id: (ms, cells, launches)} of this context's own ksw launches since it was created (classes: csrc/ksw_plan.h) — which
+        kernel a batch ran on, for a context used without a mapper"""
+        lib().wm_ksw_n_classes.restype = C.c_int
+        out = np.zeros(3 * lib().wm_ksw_n_classes(), np.float64)
+        n = C.c_int()
+        lib().wm_ctx_kernel_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        _chk(lib().wm_ctx_kernel_stats(self._h, out.ctypes.data, len(out), C.byref(n)))
+        return {k: (float(out[3 * k]), float(out[3 * k + 1]), int(out[3 * k + 2])) for k in range(n.value)}
+
     def ksw_prepare(self, score, jobs, seqs):
         jobs = np.ascontiguousarray(jobs, KSW_JOB_DTYPE)
         seqs = np.ascontiguousarray(seqs, np.uint8)
