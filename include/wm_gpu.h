@@ -287,6 +287,24 @@ int wm_window_batch(wm_ctx_t *ctx, int n, const wm_window_job_t *jobs, const uin
  * jobs[i].len, the sequence the job seeds (inside stage 1 a window's: qlen_sum of src/map.c:346-364). keys == NULL: wm_window_batch. */
 int wm_window_batch_keyed(wm_ctx_t *ctx, int n, const wm_window_job_t *jobs, const wm_qkey_t *keys, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
                           int max_occ, int64_t flag, wm_window_res_t *res, uint64_t *u_pool, size_t u_cap, size_t *u_used, wm128_t *a_pool, size_t a_cap, size_t *a_used);
+/* -T (mm_mapopt_t::sdust_thres, src/map.c:43-67,80-81): wm_window_batch_keyed with the SDUST threshold. With sdust_thres > 0 every job's minimizers are
+ * squeezed by the masked intervals of the job's sequence (sdust_core, src/sdust.c:134-164, W = 64; coordinates relative to the job's sequence) between
+ * the sketch and the seeding, on the device (csrc/sdust_kernel.h): a minimizer stays iff at most half of its span lies in masked intervals. n_mini,
+ * rep_len and everything after follow the squeezed list, as in collect_minimizers. sdust_thres <= 0: wm_window_batch_keyed — nothing more is launched
+ * or allocated. The two entries above forward here with 0. */
+int wm_window_batch_dust(wm_ctx_t *ctx, int n, const wm_window_job_t *jobs, const wm_qkey_t *keys, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
+                         int max_occ, int64_t flag, int sdust_thres, wm_window_res_t *res, uint64_t *u_pool, size_t u_cap, size_t *u_used, wm128_t *a_pool, size_t a_cap, size_t *a_used);
+/* The operator on its own: sdust_core (src/sdust.c:134-164, W = 64) of n sequences of 0..4 codes, one wavefront each; needs no index on the context.
+ * Sequence i: len[i] codes at seqs + seq_off[i], or (resident && resident[i]) at code seq_off[i] of the resident reads (wm_reads_upload). thres > 0.
+ * Intervals of sequence i: (start, finish) pairs iv[2 * iv_off[i] .. + 2 * n_iv[i]), iv_cap = pairs the pool holds (WM_ENOMEM when too small; a
+ * sequence has at most len / 4 + 24). As in the reference an interval may reach past the bases of the sequence when it holds ambiguous bases
+ * (src/sdust.c:156-160 reset the run, not the window). p_high (optional): per sequence the largest number of perfect intervals held at once
+ * (src/sdust.c:48): a wavefront's list holds 4 096; a sequence that needs more is finished by the host (csrc/host/wm_sdust.h). */
+int wm_sdust_batch(wm_ctx_t *ctx, int n, const uint8_t *seqs, size_t seqs_bytes, const uint64_t *seq_off, const int32_t *len, const uint8_t *resident, int thres,
+                   int32_t *iv, size_t iv_cap, uint64_t *iv_off, int32_t *n_iv, int32_t *p_high);
+/* process-wide account of the filter since the last reset: out5 = window calls that ran it, milliseconds of its kernel, jobs of those calls, jobs the host
+ * finished, largest list of perfect intervals seen */
+void wm_sdust_stats(double *out5, int reset);
 /* kernel time of the last sketch/seed/chain/window batch call (HIP events on the context stream), ms */
 float wm_last_aux_ms(const wm_ctx_t *ctx);
 

@@ -133,6 +133,21 @@ def build_emu_selfmap():
     return out
 
 
+def build_emu_sdust(defines=()):
+    """tests/simt_emu/libwm_emu_sdust[_<defines>].so: the two kernels of the -T filter (csrc/sdust_kernel.h) on the emulator and the host restatement
+    (csrc/host/wm_sdust.h) (tests/simt_emu/emu_sdust.cpp). ("WM_SDUST_CAP=64",) builds the variant whose list of perfect intervals overflows."""
+    emu = os.path.join(ROOT, "tests", "simt_emu")
+    tag = "".join("_" + "".join(ch if ch.isalnum() else "_" for ch in d) for d in defines)
+    out = os.path.join(emu, "libwm_emu_sdust%s.so" % tag)
+    srcs = [os.path.join(emu, f) for f in ("emu_sdust.cpp", "simt.h")] + \
+           [os.path.join(CSRC, f) for f in ("sdust_kernel.h", "sketch_kernel.h", "reads2bit.h", "wm_internal.h", os.path.join("host", "wm_sdust.h"), os.path.join("host", "wm_core.h"))]
+    with _Lock(out):
+        if _newer(out, srcs):
+            _run_to(out, lambda o: ["g++", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas"] +
+                    ["-D" + d for d in defines] + ["-I" + emu, "-I" + CSRC, "-o", o, os.path.join(emu, "emu_sdust.cpp")])
+    return out
+
+
 def build_emu_stripe(defines=()):
     """tests/simt_emu/libwm_emu_stripe[_<defines>].so: the stripe-pipelined ksw kernel alone on the emulator, with its event counters and the
     polling watchdog (tests/simt_emu/emu_stripe.cpp). ("WM_STRIPE_TEST_SLACK=...",) builds the variant whose bookkeeping margin is useless, so that
@@ -182,6 +197,7 @@ if __name__ == "__main__":
     build_oracle()
     build_emu()
     build_emu_selfmap()
+    build_emu_sdust()
     build_emu_stripe()
     build_emu_chain()
     build_harness()

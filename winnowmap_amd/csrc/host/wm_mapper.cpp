@@ -43,6 +43,7 @@ void window_and_align(Scheduler &sch, const Index &idx, const MapOpt &o, float g
 	if (sketch_it) { wr.seq = seq_codes; wr.len = qlen; wr.dev_off = seq_dev_off; }
 	wr.pre = std::move(pre);
 	wr.max_occ = o.mid_occ; wr.flag = o.flag;
+	wr.sdust_thres = o.sdust_thres;                                     // -T: every collect_minimizers call squeezes its minimizers (src/map.c:80-81)
 	if (key) { wr.has_key = true; wr.q_lo = key->lo; wr.q_eq = key->eq; }          // skip_seed (src/map.c:132-154): the read's name against the contigs'; qlen there = this request's len
 	wr.max_dist_x = max_gap_ref; wr.min_dist_x = min_gap_ref; wr.max_dist_y = max_gap_qry; wr.bw = o.bw;
 	wr.max_skip = o.max_chain_skip; wr.max_iter = o.max_chain_iter; wr.min_cnt = o.min_cnt; wr.min_sc = o.min_chain_score;

@@ -1,5 +1,6 @@
 // wm_ops.cpp — DeviceOps::window_batch composed from the per-operation batches (see wm_ops.h).
 #include "wm_ops.h"
+#include "wm_sdust.h"
 
 namespace wm {
 
@@ -11,6 +12,8 @@ void DeviceOps::window_batch(int w, int k, std::vector<WindowReq*> &reqs)
 	for (size_t i = 0; i < n; ++i)
 		if (reqs[i]->len > 0) { sk[i].seq = reqs[i]->seq; sk[i].len = reqs[i]->len; sk[i].dev_off = reqs[i]->dev_off; skp.push_back(&sk[i]); }
 	if (!skp.empty()) sketch_batch(w, k, skp);
+	for (size_t i = 0; i < n; ++i)                   // -T: collect_minimizers' squeeze (src/map.c:80-81), per request
+		if (reqs[i]->len > 0 && reqs[i]->sdust_thres > 0) dust_minimizers(sk[i].mini, reqs[i]->seq, reqs[i]->len, reqs[i]->sdust_thres);
 	// collect_seed_hits takes one (max_occ, flag) per batch: group the requests (one group in practice)
 	std::vector<SeedReq> sd(n);
 	std::vector<char> done(n, 0);

@@ -44,6 +44,7 @@ struct WindowReq {
 	int64_t dev_off = -1;                  // offset of seq[0] in the resident read codes, -1 = not resident (the view is staged)
 	std::vector<m128> pre;                 // in
 	int max_occ = 0; int64_t flag = 0;     // collect_seed_hits
+	int sdust_thres = 0;                   // > 0: mm_dust_minier squeezes the minimizers before the seeding (src/map.c:43-67, 80-81)
 	int max_dist_x = 0, min_dist_x = 0, max_dist_y = 0, bw = 0, max_skip = 0, max_iter = 0, min_cnt = 0, min_sc = 0;   // mm_chain_dp
 	float gap_scale = 1.0f;
 	bool is_cdna = false;

@@ -121,10 +121,10 @@ struct GpuOpsCtx {
 	{
 		const int n = (int)reqs.size();
 		if (n == 0) return;
-		for (int i = 1; i < n; ++i)             // collect_seed_hits takes one (max_occ, flag) per call: requests that differ go in their own call
-			if (reqs[i]->max_occ != reqs[0]->max_occ || reqs[i]->flag != reqs[0]->flag) {
+		for (int i = 1; i < n; ++i)             // collect_seed_hits takes one (max_occ, flag), the -T filter one threshold per call: requests that differ go in their own call
+			if (reqs[i]->max_occ != reqs[0]->max_occ || reqs[i]->flag != reqs[0]->flag || reqs[i]->sdust_thres != reqs[0]->sdust_thres) {
 				std::vector<wm::WindowReq*> same, rest;
-				for (wm::WindowReq *r : reqs) (r->max_occ == reqs[0]->max_occ && r->flag == reqs[0]->flag ? same : rest).push_back(r);
+				for (wm::WindowReq *r : reqs) (r->max_occ == reqs[0]->max_occ && r->flag == reqs[0]->flag && r->sdust_thres == reqs[0]->sdust_thres ? same : rest).push_back(r);
 				window_batch(same);
 				if (error.empty()) window_batch(rest);
 				return;
@@ -158,7 +158,7 @@ struct GpuOpsCtx {
 		for (int round = 0; round < 2; ++round) {
 			ArenaMark mark(c);
 			WinDev D;
-			int rc = window_launch(c, n, jobs.data(), seqs.data(), stage, pre.data(), npre, reqs[0]->max_occ, reqs[0]->flag, round == 1, D, keys.empty() ? 0 : keys.data());
+			int rc = window_launch(c, n, jobs.data(), seqs.data(), stage, pre.data(), npre, reqs[0]->max_occ, reqs[0]->flag, round == 1, D, keys.empty() ? 0 : keys.data(), reqs[0]->sdust_thres);
 			if (!rc) rc = window_verdict(D, round);
 			if (rc < 0) { fail("window"); return; }
 			if (rc == 1) continue;

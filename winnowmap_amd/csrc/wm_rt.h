@@ -139,6 +139,6 @@ int sketch_launch(wm_ctx_t *c, int n, const wm_sketch_job_t *h_jobs, const wm_sk
 // wm_window.hip
 struct WinDev { wm_win_res_t *d_res; uint64_t *d_upool; wm128_t *d_vpool; uint64_t *d_ctr; uint64_t ctr[4]; uint32_t tot[3]; };
 int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
-                  int max_occ, int64_t flag, bool slot_full, WinDev &D, const wm_qkey_t *keys = 0);
+                  int max_occ, int64_t flag, bool slot_full, WinDev &D, const wm_qkey_t *keys = 0, int sdust_thres = 0);
 int window_fetch(wm_ctx_t *c, const WinDev &D, int n, wm_window_res_t *res, uint64_t *u_pool, wm128_t *a_pool);
 int window_verdict(const WinDev &D, int round);

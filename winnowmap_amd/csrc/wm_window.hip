@@ -6,7 +6,132 @@
 #include "sketch_kernel.h"
 #include "seedchain_kernel.h"
 #include "window_kernel.h"
+#include "sdust_kernel.h"
 #include "host/wm_core.h"
+#include "host/wm_sdust.h"
+
+// ======================================================================================================
+// -T: the SDUST intervals of a sequence and the squeeze of its minimizers (sdust_kernel.h; mm_dust_minier, src/map.c:43-67)
+// ======================================================================================================
+// entries of the list of perfect intervals a wavefront keeps in LDS; WM_SDUST_CAP in the environment (64 .. the compiled size) shrinks it so that the
+// tests reach the path on which the host finishes a job. Read per call.
+static int sdust_list_cap()
+{
+	const char *e = getenv("WM_SDUST_CAP");
+	const int v = e ? atoi(e) : WM_SDUST_CAP;
+	return v < 64 ? 64 : v > WM_SDUST_CAP ? WM_SDUST_CAP : v;
+}
+// process-wide account of the filter (wm_sdust_stats): window calls that ran it, microseconds of win_dust_kernel, jobs it saw, jobs the host finished, largest list
+static std::atomic<uint64_t> g_dust_calls{0}, g_dust_us{0}, g_dust_jobs{0}, g_dust_host{0};
+static std::atomic<int> g_dust_high{0};
+// WM_SDUST_REPORT=1: the account on stderr when the library is unloaded (a command-line front end has no other way to ask)
+static struct DustReport {
+	~DustReport()
+	{
+		if (!getenv("WM_SDUST_REPORT") || !g_dust_calls.load()) return;
+		const double calls = (double)g_dust_calls.load(), ms = (double)g_dust_us.load() * 1e-3;
+		fprintf(stderr, "[wm] sdust: %.0f window calls, dust kernel %.3f ms in all = %.4f ms per call, %.0f jobs, %.0f finished by the host, largest list %d\n",
+		        calls, ms, ms / calls, (double)g_dust_jobs.load(), (double)g_dust_host.load(), g_dust_high.load());
+	}
+} g_dust_report;
+static void dust_note_high(int h) { int cur = g_dust_high.load(); while (h > cur && !g_dust_high.compare_exchange_weak(cur, h)) {} }
+
+// job j: intervals of its sequence -> iv_pool[2 * out_off ..), at most cap pairs; iv_cnt[j] = how many, -1 = finish it on the host; high[j] = largest list held
+__global__ __launch_bounds__(64) void sdust_kernel(const wm_sketch_job_t *__restrict__ jobs, const uint8_t *seqs, const uint64_t *rpk, const uint64_t *rnm, int T, int p_cap,
+                                                    int *iv_pool, int *iv_cnt, int *high)
+{
+	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+	const int j = blockIdx.x;
+	const wm_sketch_job_t s = jobs[j];
+	int hi = 0;
+	const int n = wmk::sdust_wave(seqs, rpk, rnm, (long long)s.seq_off, s.len, T, (int*)smem, p_cap, iv_pool + 2 * s.out_off, s.cap, &hi);
+	if (threadIdx.x == 0) { iv_cnt[j] = n; high[j] = hi; }
+}
+// the window call's step between the sketch and the seeding: job j's minimizers mini[out_off .. + mcnt[j]) are squeezed in place and mcnt[j] rewritten.
+// The intervals live in the job's slice of the sketch's order scratch (dead by now: 8 B per base = one interval per base). A job whose minimizer
+// slot overflowed is left to the full-size retry. stat[0]: jobs the host must finish, listed from stat[2] on; stat[1]: largest list held.
+__global__ __launch_bounds__(64) void win_dust_kernel(const wm_sketch_job_t *__restrict__ sj, const uint8_t *seqs, const uint64_t *rpk, const uint64_t *rnm, int T, int p_cap,
+                                                       wm128_t *mini, int *mcnt, double *so, int *stat)
+{
+	WM_SETPRIO(2);
+	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+	const int j = blockIdx.x;
+	const wm_sketch_job_t s = sj[j];
+	const int n_mini = mcnt[j];
+	if (s.len <= 0 || n_mini <= 0 || n_mini > s.cap) return;
+	int *iv = (int*)(so + s.scratch_off);
+	int hi = 0;
+	const int n_iv = wmk::sdust_wave(seqs, rpk, rnm, (long long)s.seq_off, s.len, T, (int*)smem, p_cap, iv, s.len, &hi);
+	if (threadIdx.x == 0) atomicMax(stat + 1, hi);
+	if (n_iv < 0) {
+		if (threadIdx.x == 0) stat[2 + atomicAdd(stat, 1)] = j;
+		return;
+	}
+	simt::mem_sync();                                // lane 0 wrote the intervals, every lane reads them
+	const int k = wmk::dust_filter_wave(mini + s.out_off, n_mini, iv, n_iv);
+	if (threadIdx.x == 0) mcnt[j] = k;
+}
+// the codes of the listed jobs as bytes, wherever they live (staged bytes or the packed resident reads): out + stride * scratch_off
+__global__ __launch_bounds__(64) void dust_codes_kernel(const wm_sketch_job_t *__restrict__ jobs, const int *list, const uint8_t *seqs, const uint64_t *rpk, const uint64_t *rnm,
+                                                         uint8_t *out, int stride)
+{
+	const wm_sketch_job_t s = jobs[list[blockIdx.x]];
+	uint8_t *o = out + (size_t)stride * s.scratch_off;
+	for (int i = threadIdx.x; i < s.len; i += 64) o[i] = (uint8_t)wmk::sk_code(seqs, rpk, rnm, (long long)s.seq_off, (long long)i);
+}
+// the codes of the n_list jobs listed at d_list (host copy: list), fetched to the host
+static int dust_fetch_codes(wm_ctx_t *c, const wm_sketch_job_t *h_jobs, const wm_sketch_job_t *d_jobs, const int *list, const int *d_list, int n_list, const uint8_t *d_seqs,
+                            uint8_t *d_out, int stride, std::vector<std::vector<uint8_t>> &codes)
+{
+	hipLaunchKernelGGL(dust_codes_kernel, dim3(n_list), dim3(64), 0, c->stream, d_jobs, d_list, d_seqs, c->d_reads, c->d_reads_nm, d_out, stride);
+	HIPCHK(hipGetLastError());
+	HIPCHK(ctx_sync(c));
+	codes.resize((size_t)n_list);
+	for (int q = 0; q < n_list; ++q) {
+		const wm_sketch_job_t &s = h_jobs[list[q]];
+		codes[q].resize((size_t)s.len + 1);
+		HIPCHK(hipMemcpy(codes[q].data(), d_out + (size_t)stride * s.scratch_off, (size_t)s.len, hipMemcpyDeviceToHost));
+	}
+	return WM_OK;
+}
+
+// the filter of a window call (threshold > 0), queued behind the sketch; waits once for the list of jobs the host has to finish (none in practice)
+static int window_dust(wm_ctx_t *c, int n, const wm_sketch_job_t *h_sj, const wm_sketch_job_t *d_sj, const uint8_t *d_seqs, int thres, wm128_t *d_mini, int *d_mcnt,
+                       double *d_so, uint64_t *d_sx, int *d_stat)
+{
+	const int p_cap = sdust_list_cap();
+	HIPCHK(hipMemsetAsync(d_stat, 0, 8, c->stream));
+	HIPCHK(hipEventRecord(c->ev[2], c->stream));
+	hipLaunchKernelGGL(win_dust_kernel, dim3(n), dim3(64), (size_t)3 * p_cap * 4, c->stream, d_sj, d_seqs, c->d_reads, c->d_reads_nm, thres, p_cap, d_mini, d_mcnt, d_so, d_stat);
+	HIPCHK(hipEventRecord(c->ev[3], c->stream));
+	HIPCHK(hipGetLastError());
+	int st_pageable[2] = { 0, 0 };
+	int *st = c->pin_small ? c->pin_small + 20 : st_pageable;
+	HIPCHK(hipMemcpyAsync(st, d_stat, 8, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(ctx_sync(c));
+	float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+	g_dust_calls += 1; g_dust_us += (uint64_t)(ms * 1e3f); g_dust_jobs += (uint64_t)n; g_dust_host += (uint64_t)st[0];
+	dust_note_high(st[1]);
+	const int n_host = st[0];
+	if (n_host <= 0) return WM_OK;
+	// the host finishes these jobs (host/wm_sdust.h): their codes and minimizers travel down, the squeezed lists and their sizes back
+	std::vector<int> list((size_t)n_host), cnt((size_t)n);
+	HIPCHK(hipMemcpy(list.data(), d_stat + 2, (size_t)n_host * 4, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(cnt.data(), d_mcnt, (size_t)n * 4, hipMemcpyDeviceToHost));
+	std::vector<std::vector<uint8_t>> codes;
+	if (const int rc = dust_fetch_codes(c, h_sj, d_sj, list.data(), d_stat + 2, n_host, d_seqs, (uint8_t*)d_sx, 8, codes)) return rc;
+	for (int q = 0; q < n_host; ++q) {
+		const int j = list[q];
+		const wm_sketch_job_t &s = h_sj[j];
+		std::vector<wm::m128> mini((size_t)cnt[j]);
+		HIPCHK(hipMemcpy(mini.data(), d_mini + s.out_off, mini.size() * sizeof(wm128_t), hipMemcpyDeviceToHost));
+		wm::dust_minimizers(mini, codes[q].data(), s.len, thres);
+		const int k = (int)mini.size();
+		if (k) HIPCHK(hipMemcpy(d_mini + s.out_off, mini.data(), (size_t)k * sizeof(wm128_t), hipMemcpyHostToDevice));
+		HIPCHK(hipMemcpy(d_mcnt + j, &k, 4, hipMemcpyHostToDevice));
+	}
+	return WM_OK;
+}
 
 // ======================================================================================================
 // wm_window_batch: sketch → seed → sort → chain fill → chain extraction of n jobs, resident in HBM (window_kernel.h)
@@ -201,7 +326,7 @@ __global__ __launch_bounds__(64) void win_extract_kernel(const wm_win_job_t *__r
 
 // device side of one call: everything up to the dense result pools; the caller copies them out. slot_full: full-size minimizer slots (retry)
 int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
-                         int max_occ, int64_t flag, bool slot_full, WinDev &D, const wm_qkey_t *keys)
+                         int max_occ, int64_t flag, bool slot_full, WinDev &D, const wm_qkey_t *keys, int sdust_thres)
 {
 	const int w = c->skp.w;
 	(void)w;
@@ -255,6 +380,8 @@ int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t
 	static const bool ties_on_host = !(getenv("WM_WINDOW_TIES_HOST") && atoi(getenv("WM_WINDOW_TIES_HOST")) == 0);      // (0: the literal replay on the device, as until round 4; A/B)
 	int *d_tie = ties_on_host ? (int*)arena_take(c, (size_t)(8 + 8 * (size_t)n) * 4) : 0;
 	if (ties_on_host && !d_tie) return set_err(WM_ENOMEM, "window batch does not fit the arena");
+	int *d_dstat = sdust_thres > 0 ? (int*)arena_take(c, (size_t)(2 + (size_t)n) * 4 + 64) : 0;      // -T: win_dust_kernel's counters and list
+	if (sdust_thres > 0 && !d_dstat) return set_err(WM_ENOMEM, "window batch does not fit the arena");
 	uint64_t *d_ctr = (uint64_t*)arena_take(c, 64);          // [0] anchors used, [1] chains in the result pool, [2] anchors in the result pool, [3] worst err (int), [4..5] the four class counts (ints)
 	if (!d_jobs || !d_sj || !d_ord || !d_seqs || !d_pre || !d_so || !d_sx || !d_sy || !d_sl || !d_mini || !d_mcnt || !d_occ || !d_emit || !d_first || !D.d_res || !d_cj || !d_lists || !d_ctr)
 		return set_err(WM_ENOMEM, "window batch does not fit the arena");
@@ -286,6 +413,8 @@ int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t
 	if (d_tie) HIPCHK(hipMemsetAsync(d_tie, 0, 32, c->stream));
 	HIPCHK(hipEventRecord(c->ev[0], c->stream));
 	if (const int rc = sketch_launch(c, n, sj.data(), d_sj, d_ord, d_seqs, d_so, d_sx, d_sy, d_sl, d_mini, d_mcnt, !slot_full, d_long, long_bytes)) return rc;
+	// -T (mm_dust_minier in collect_minimizers, src/map.c:80-81): the minimizers are squeezed before the seeding sees them — n_mini, rep_len and all that follows
+	if (sdust_thres > 0) if (const int rc = window_dust(c, n, sj.data(), d_sj, d_seqs, sdust_thres, d_mini, d_mcnt, d_so, d_sx, d_dstat)) return rc;
 	wm_index_view_t ix = { c->d_hkey, c->d_hval, c->d_P, c->hbits, 0, c->d_name_rank, c->d_seq_len };
 	hipLaunchKernelGGL(win_seed_kernel, dim3(n), dim3(64), 0, c->stream, ix, d_jobs, d_sj, d_mcnt, d_mini, d_pre, d_occ, d_first, d_emit, d_a, d_ctr, cap, D.d_res, (int*)(d_ctr + 3));
 	const size_t ws_bytes = (size_t)wmk::WIN_WS_PAD * 4;
@@ -398,6 +527,12 @@ extern "C" int wm_window_batch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, 
 
 extern "C" int wm_window_batch_keyed(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const wm_qkey_t *keys, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
                                      int max_occ, int64_t flag, wm_window_res_t *res, uint64_t *u_pool, size_t u_cap, size_t *u_used, wm128_t *a_pool, size_t a_cap, size_t *a_used)
+{
+	return wm_window_batch_dust(c, n, jobs, keys, seqs, seqs_bytes, pre, n_pre_total, max_occ, flag, 0, res, u_pool, u_cap, u_used, a_pool, a_cap, a_used);
+}
+
+extern "C" int wm_window_batch_dust(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const wm_qkey_t *keys, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
+                                    int max_occ, int64_t flag, int sdust_thres, wm_window_res_t *res, uint64_t *u_pool, size_t u_cap, size_t *u_used, wm128_t *a_pool, size_t a_cap, size_t *a_used)
 try {
 	if (u_used) *u_used = 0;
 	if (a_used) *a_used = 0;
@@ -409,7 +544,7 @@ try {
 	for (int round = 0; round < 2; ++round) {
 		ArenaMark mark(c);
 		WinDev D;
-		int rc = window_launch(c, n, jobs, seqs, seqs_bytes, pre, n_pre_total, max_occ, flag, round == 1, D, keys);
+		int rc = window_launch(c, n, jobs, seqs, seqs_bytes, pre, n_pre_total, max_occ, flag, round == 1, D, keys, sdust_thres);
 		if (rc) return rc;
 		rc = window_verdict(D, round);
 		if (rc < 0) return rc;
@@ -424,3 +559,79 @@ try {
 }
 catch (const std::bad_alloc &) { return set_err(WM_ENOMEM, "out of host memory"); }
 
+
+// ======================================================================================================
+// wm_sdust_batch: the operator on its own
+// ======================================================================================================
+extern "C" int wm_sdust_batch(wm_ctx_t *c, int n, const uint8_t *seqs, size_t seqs_bytes, const uint64_t *seq_off, const int32_t *len, const uint8_t *resident, int thres,
+                              int32_t *iv, size_t iv_cap, uint64_t *iv_off, int32_t *n_iv, int32_t *p_high)
+try {
+	if (!c) return set_err(WM_EINVAL, "null context");
+	if (n <= 0) return WM_OK;
+	if (!seq_off || !len || !iv_off || !n_iv || (!seqs && seqs_bytes)) return set_err(WM_EINVAL, "null argument");
+	if (thres <= 0) return set_err(WM_EINVAL, "wm_sdust_batch needs a threshold > 0 (got %d)", thres);
+	HIPCHK(hipSetDevice(c->device));
+	ArenaMark mark(c);
+	std::vector<wm_sketch_job_t> jb((size_t)n);
+	uint64_t slots = 0, bases = 0;
+	for (int i = 0; i < n; ++i) {
+		const bool res = resident && resident[i];
+		if (len[i] < 0 || (res ? (!c->d_reads || seq_off[i] + (uint64_t)len[i] > c->reads_bytes) : (seq_off[i] + (uint64_t)len[i] > seqs_bytes))) return set_err(WM_EINVAL, "sequence %d outside its buffer", i);
+		jb[i].seq_off = res ? (WM_RD_PACKED_BIT | seq_off[i]) : seq_off[i]; jb[i].len = len[i];
+		jb[i].cap = len[i] / 4 + 24;                                   // intervals are disjoint, apart and at least three bases long, and end at most a window past the sequence
+		jb[i].out_off = slots; slots += (uint64_t)jb[i].cap;
+		jb[i].scratch_off = bases; bases += (uint64_t)len[i];
+	}
+	const int p_cap = sdust_list_cap();
+	wm_sketch_job_t *d_jobs = (wm_sketch_job_t*)arena_take(c, (size_t)n * sizeof(wm_sketch_job_t));
+	uint8_t *d_seqs = (uint8_t*)arena_take(c, seqs_bytes + 64);
+	int *d_iv = (int*)arena_take(c, (size_t)(slots + 1) * 8), *d_cnt = (int*)arena_take(c, (size_t)n * 4 + 64), *d_high = (int*)arena_take(c, (size_t)n * 4 + 64);
+	if (!d_jobs || !d_seqs || !d_iv || !d_cnt || !d_high) return set_err(WM_ENOMEM, "sdust batch does not fit the arena");
+	HIPCHK(hipMemcpyAsync(d_jobs, jb.data(), (size_t)n * sizeof(wm_sketch_job_t), hipMemcpyHostToDevice, c->stream));
+	if (seqs_bytes) HIPCHK(hipMemcpyAsync(d_seqs, seqs, seqs_bytes, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipEventRecord(c->ev[0], c->stream));
+	hipLaunchKernelGGL(sdust_kernel, dim3(n), dim3(64), (size_t)3 * p_cap * 4, c->stream, d_jobs, d_seqs, c->d_reads, c->d_reads_nm, thres, p_cap, d_iv, d_cnt, d_high);
+	HIPCHK(hipEventRecord(c->ev[1], c->stream));
+	HIPCHK(hipGetLastError());
+	std::vector<int> cnt((size_t)n), high((size_t)n);
+	std::vector<int32_t> tmp((size_t)(slots + 1) * 2);
+	HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(high.data(), d_high, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(tmp.data(), d_iv, (size_t)slots * 8, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(ctx_sync(c));
+	float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1])); c->aux_ms = ms;
+	// jobs whose list overflowed: finished by the host restatement
+	std::vector<int> list;
+	for (int i = 0; i < n; ++i) if (cnt[i] < 0) list.push_back(i);
+	std::vector<std::vector<wm::DustIv>> hiv(list.size());
+	if (!list.empty()) {
+		int *d_list = (int*)arena_take(c, list.size() * 4 + 64);
+		uint8_t *d_codes = (uint8_t*)arena_take(c, (size_t)bases + 64);
+		if (!d_list || !d_codes) return set_err(WM_ENOMEM, "sdust batch does not fit the arena");
+		HIPCHK(hipMemcpy(d_list, list.data(), list.size() * 4, hipMemcpyHostToDevice));
+		std::vector<std::vector<uint8_t>> codes;
+		if (const int rc = dust_fetch_codes(c, jb.data(), d_jobs, list.data(), d_list, (int)list.size(), d_seqs, d_codes, 1, codes)) return rc;
+		for (size_t q = 0; q < list.size(); ++q) high[list[q]] = wm::sdust_intervals(codes[q].data(), len[list[q]], thres, hiv[q]);
+		g_dust_host += (uint64_t)list.size();
+	}
+	size_t used = 0, q = 0;
+	for (int i = 0; i < n; ++i) {
+		const bool host = cnt[i] < 0;
+		const size_t k = host ? hiv[q].size() : (size_t)cnt[i];
+		if (used + k > iv_cap || (k && !iv)) return set_err(WM_ENOMEM, "interval output pool too small");
+		iv_off[i] = used; n_iv[i] = (int32_t)k;
+		if (host) { for (size_t t = 0; t < k; ++t) { iv[2 * (used + t)] = hiv[q][t].st; iv[2 * (used + t) + 1] = hiv[q][t].en; } ++q; }
+		else if (k) memcpy(iv + 2 * used, tmp.data() + 2 * jb[i].out_off, k * 8);
+		used += k;
+		if (p_high) p_high[i] = high[i];
+		dust_note_high(high[i]);
+	}
+	return WM_OK;
+}
+catch (const std::bad_alloc &) { return set_err(WM_ENOMEM, "out of host memory"); }
+
+extern "C" void wm_sdust_stats(double *out5, int reset)
+{
+	if (out5) { out5[0] = (double)g_dust_calls.load(); out5[1] = (double)g_dust_us.load() * 1e-3; out5[2] = (double)g_dust_jobs.load(); out5[3] = (double)g_dust_host.load(); out5[4] = (double)g_dust_high.load(); }
+	if (reset) { g_dust_calls = 0; g_dust_us = 0; g_dust_jobs = 0; g_dust_host = 0; g_dust_high = 0; }
+}

@@ -169,6 +169,41 @@ class Context:
                                      max_occ, flag, res.ctypes.data, u_pool.ctypes.data, u_cap, C.byref(uu), a_pool.ctypes.data, a_cap, C.byref(au)))
         return res, u_pool[:uu.value], a_pool[:au.value]
 
+    def window_batch_dust(self, jobs, keys, seqs, pre, max_occ, flag, sdust_thres, u_cap, a_cap):
+        """wm_window_batch_dust: window_batch_keyed with the -T threshold — with sdust_thres > 0 every job's minimizers are squeezed by the SDUST intervals of
+        its sequence before the seeding (mm_dust_minier, src/map.c:43-67); 0 = window_batch_keyed. Same arguments and results otherwise."""
+        L = lib()
+        L.wm_window_batch_dust.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int64, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        n = len(jobs)
+        jobs = np.ascontiguousarray(jobs, WINDOW_JOB)
+        keys = None if keys is None else np.ascontiguousarray(keys, np.uint32).reshape(n, 2)
+        seqs = np.ascontiguousarray(seqs, np.uint8)
+        pre = np.ascontiguousarray(pre, np.uint64).reshape(-1, 2)
+        res = np.zeros(n, WINDOW_RES)
+        u_pool, a_pool = np.zeros(u_cap + 1, np.uint64), np.zeros((a_cap + 1, 2), np.uint64)
+        uu, au = C.c_size_t(), C.c_size_t()
+        _chk(L.wm_window_batch_dust(self._h, n, jobs.ctypes.data, None if keys is None else keys.ctypes.data, seqs.ctypes.data, seqs.nbytes, pre.ctypes.data, len(pre),
+                                    max_occ, flag, sdust_thres, res.ctypes.data, u_pool.ctypes.data, u_cap, C.byref(uu), a_pool.ctypes.data, a_cap, C.byref(au)))
+        return res, u_pool[:uu.value], a_pool[:au.value]
+
+    def sdust_batch(self, seqs, seq_off, lens, thres, resident=None):
+        """wm_sdust_batch: the SDUST intervals (sdust_core with W = 64, src/sdust.c:134-164) of n sequences of 0..4 codes. seqs: uint8 staging codes; sequence i
+        is lens[i] codes at seq_off[i] of seqs, or of the resident reads where resident[i] != 0 (reads_upload). Returns (list of int32 [n_i, 2] arrays of
+        (start, finish), high int32 [n] = the largest list of perfect intervals each sequence needed)."""
+        L = lib()
+        L.wm_sdust_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        seqs = np.ascontiguousarray(seqs, np.uint8)
+        seq_off, lens = np.ascontiguousarray(seq_off, np.uint64), np.ascontiguousarray(lens, np.int32)
+        n = len(lens)
+        res = None if resident is None else np.ascontiguousarray(resident, np.uint8)
+        cap = int((lens.astype(np.int64) // 4 + 24).sum()) + 1
+        iv = np.zeros((cap, 2), np.int32)
+        iv_off, n_iv, high = np.zeros(n, np.uint64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        _chk(L.wm_sdust_batch(self._h, n, seqs.ctypes.data, seqs.nbytes, seq_off.ctypes.data, lens.ctypes.data, None if res is None else res.ctypes.data, thres,
+                              iv.ctypes.data, cap, iv_off.ctypes.data, n_iv.ctypes.data, high.ctypes.data))
+        return [iv[int(iv_off[i]):int(iv_off[i]) + int(n_iv[i])].copy() for i in range(n)], high
+
     def kernel_stats(self):
         """wm_ctx_kernel_stats: {class id: (ms, cells, launches)} of this context's own ksw launches since it was created (classes: csrc/ksw_plan.h) — which
         kernel a batch ran on, for a context used without a mapper"""
@@ -237,6 +272,15 @@ def set_ksw_dual(on):
 def ksw_dual_enabled():
     lib().wm_ksw_dual_enabled.restype = C.c_int
     return bool(lib().wm_ksw_dual_enabled())
+
+
+def sdust_stats(reset=False):
+    """wm_sdust_stats: the -T filter's process-wide account since the last reset"""
+    out = np.zeros(5, np.float64)
+    lib().wm_sdust_stats.argtypes = [C.c_void_p, C.c_int]
+    lib().wm_sdust_stats.restype = None
+    lib().wm_sdust_stats(out.ctypes.data, 1 if reset else 0)
+    return {"window_calls": int(out[0]), "kernel_ms": float(out[1]), "jobs": int(out[2]), "host_jobs": int(out[3]), "list_high": int(out[4])}
 
 
 def build_defines():
