@@ -243,7 +243,11 @@ int wm_sketch_batch(wm_ctx_t *ctx, int n, const uint8_t *seqs, size_t seqs_bytes
 int wm_sketch_set_filter(wm_ctx_t *ctx, const uint8_t *bits, size_t n_bytes, uint64_t table_bits, uint32_t salt0, uint32_t salt1, int k, int w);
 /* collect_seed_hits: minimizers of job i are mini[mini_off[i] .. +n_mini[i]); anchors (sorted by x with the
  * reference's radix_sort_128x permutation) go to out[out_off[i] .. +n_anchors[i]); rep_len as src/map.c:126.
- * flag: MM_F_FOR_ONLY / MM_F_REV_ONLY are honoured. MM_F_NO_DIAG (0x1) / MM_F_NO_DUAL (0x2) are IGNORED here, as skip_seed
+ * flag: MM_F_FOR_ONLY / MM_F_REV_ONLY are honoured. MM_F_HEAP_SORT (0x400000, --heap-sort=yes) is honoured: the anchors come in the order of
+ * collect_seed_hits_heap (src/map.c:156-220) instead — sorted by x as well, but where anchors share x in the order in which the reference's binary
+ * heap pops them, not in radix_sort_128x's tie permutation. On the device: a job whose x are all distinct is sorted, a job with equal x replays the
+ * heap literally (one lane pops, the wavefront places the anchors); nothing of it is launched or allocated by a call without the bit.
+ * MM_F_NO_DIAG (0x1) / MM_F_NO_DUAL (0x2) are IGNORED here, as skip_seed
  * (src/map.c:132-154) ignores them when qname == NULL (:135): this entry point has no query names. See wm_seed_batch_keyed. */
 int wm_seed_batch(wm_ctx_t *ctx, int n, const wm128_t *mini, const uint64_t *mini_off, const int32_t *n_mini, const int32_t *qlen,
                   int max_occ, int64_t flag, wm128_t *out, size_t out_cap, uint64_t *out_off, int32_t *n_anchors, int32_t *rep_len);
@@ -282,7 +286,8 @@ typedef struct {
 typedef struct { int32_t n_anchors, rep_len, n_mini, n_u, n_v; uint32_t u_off, a_off; } wm_window_res_t;
 int wm_window_batch(wm_ctx_t *ctx, int n, const wm_window_job_t *jobs, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
                     int max_occ, int64_t flag, wm_window_res_t *res, uint64_t *u_pool, size_t u_cap, size_t *u_used, wm128_t *a_pool, size_t a_cap, size_t *a_used);
-/* flag: as wm_seed_batch — MM_F_NO_DIAG / MM_F_NO_DUAL are ignored without query names (skip_seed with qname == NULL, src/map.c:132-154).
+/* flag: as wm_seed_batch — MM_F_HEAP_SORT: the seeded anchors of every job are collect_seed_hits_heap's list (no sort follows them, src/map.c:811; the union
+ * with handed-in anchors is still sorted, :833, with the heap-ordered part as that unstable sort's input). MM_F_NO_DIAG / MM_F_NO_DUAL are ignored without query names (skip_seed with qname == NULL, src/map.c:132-154).
  * wm_window_batch_keyed: one key per job (wm_index_query_key), the two bits are served; the length skip_seed compares a contig's with is
  * jobs[i].len, the sequence the job seeds (inside stage 1 a window's: qlen_sum of src/map.c:346-364). keys == NULL: wm_window_batch. */
 int wm_window_batch_keyed(wm_ctx_t *ctx, int n, const wm_window_job_t *jobs, const wm_qkey_t *keys, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,

@@ -133,6 +133,21 @@ def build_emu_selfmap():
     return out
 
 
+def build_emu_heapseed():
+    """tests/simt_emu/libwm_emu_heapseed.so: the two seeding kernels with the ordering stage of --heap-sort=yes (csrc/window_kernel.h: heap_order_block) on the
+    emulator, with its event counters, and the host restatement of collect_seed_hits_heap (csrc/host/wm_core.cpp) (tests/simt_emu/emu_heapseed.cpp)."""
+    emu = os.path.join(ROOT, "tests", "simt_emu")
+    out = os.path.join(emu, "libwm_emu_heapseed.so")
+    core = os.path.join(CSRC, "host", "wm_core.cpp")
+    srcs = [os.path.join(emu, f) for f in ("emu_heapseed.cpp", "simt.h")] + [core] + \
+           [os.path.join(CSRC, f) for f in ("seedchain_kernel.h", "window_kernel.h", "wm_internal.h", os.path.join("host", "wm_core.h"))]
+    with _Lock(out):
+        if _newer(out, srcs):
+            _run_to(out, lambda o: ["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-pthread", "-ffp-contract=off", "-Wno-unknown-pragmas",
+                                    "-I" + emu, "-I" + CSRC, "-o", o, os.path.join(emu, "emu_heapseed.cpp"), core])
+    return out
+
+
 def build_emu_sdust(defines=()):
     """tests/simt_emu/libwm_emu_sdust[_<defines>].so: the two kernels of the -T filter (csrc/sdust_kernel.h) on the emulator and the host restatement
     (csrc/host/wm_sdust.h) (tests/simt_emu/emu_sdust.cpp). ("WM_SDUST_CAP=64",) builds the variant whose list of perfect intervals overflows."""
@@ -197,6 +212,7 @@ if __name__ == "__main__":
     build_oracle()
     build_emu()
     build_emu_selfmap()
+    build_emu_heapseed()
     build_emu_sdust()
     build_emu_stripe()
     build_emu_chain()

@@ -185,6 +185,87 @@ void radix_sort_128x(m128 *beg, m128 *end) { FlagSort<m128, KeyX>().run(beg, end
 void radix_sort_128x_parallel(m128 *beg, m128 *end, int n_threads) { FlagSort<m128, KeyX>().run_parallel(beg, end, n_threads); }
 void radix_sort_64(uint64_t *beg, uint64_t *end) { FlagSort<uint64_t, KeyId>().run(beg, end); }
 
+// skip_seed, src/map.c:132-154; strcmp(qname, contig name) through the name ranks: cmp == 0 <=> q_eq && rank == q_lo, cmp > 0 <=> rank < q_lo (wm_names.h)
+bool skip_seed(const SeedSkip &k, uint64_t r, uint32_t q_pos, int qlen, bool *is_self)
+{
+	*is_self = false;
+	if (k.has_key && (k.flag & (F_NO_DIAG | F_NO_DUAL))) {
+		const uint32_t rk = k.name_rank[r >> 32];
+		if ((k.flag & F_NO_DIAG) && k.q_eq && rk == k.q_lo && (int)k.seq_len[r >> 32] == qlen) {
+			if ((uint32_t)r >> 1 == (q_pos >> 1)) return true;
+			if ((r & 1) == (q_pos & 1)) *is_self = true;
+		}
+		if ((k.flag & F_NO_DUAL) && rk < k.q_lo) return true;
+	}
+	if (k.flag & (F_FOR_ONLY | F_REV_ONLY)) {
+		if ((r & 1) == (q_pos & 1)) { if (k.flag & F_REV_ONLY) return true; }
+		else if (k.flag & F_FOR_ONLY) return true;
+	}
+	return false;
+}
+
+// KSORT_INIT(heap, mm128_t, heap_lt), src/ksort.h:43-59: the smallest x at the root; on equal children the left one, and an entry sinks past equal keys
+void ks_heapdown_heap(size_t i, size_t n, m128 *l)
+{
+	size_t k = i;
+	const m128 tmp = l[i];
+	while ((k = (k << 1) + 1) < n) {
+		if (k != n - 1 && l[k].x > l[k + 1].x) ++k;
+		if (l[k].x > tmp.x) break;
+		l[i] = l[k]; i = k;
+	}
+	l[i] = tmp;
+}
+void ks_heapmake_heap(size_t n, m128 *l)
+{
+	for (size_t i = (n >> 1) - 1; i != (size_t)-1; --i) ks_heapdown_heap(i, n, l);
+}
+
+// collect_seed_hits_heap after collect_matches, src/map.c:166-219
+int64_t seed_hits_heap(const HeapMatch *m, int n_m, int64_t n_a, int qlen, const SeedSkip &sk, m128 *a)
+{
+	std::vector<m128> heap((size_t)(n_m > 0 ? n_m : 0) + 1);
+	size_t heap_size = 0;
+	int64_t n_for = 0, n_rev = 0;
+	for (int i = 0; i < n_m; ++i)                                                  // :169-175
+		if (m[i].n > 0) { heap[heap_size].x = m[i].cr[0]; heap[heap_size].y = (uint64_t)i << 32; ++heap_size; }
+	ks_heapmake_heap(heap_size, heap.data());
+	while (heap_size > 0) {                                                        // :177-205
+		const HeapMatch *q = &m[heap[0].y >> 32];
+		const uint64_t r = heap[0].x;
+		const uint32_t rpos = (uint32_t)r >> 1;
+		bool is_self;
+		if (!skip_seed(sk, r, q->q_pos, qlen, &is_self)) {
+			m128 *p;
+			if ((r & 1) == (q->q_pos & 1)) {
+				p = &a[n_for++];
+				p->x = (r & 0xffffffff00000000ULL) | rpos;
+				p->y = (uint64_t)q->q_span << 32 | q->q_pos >> 1;
+			} else {
+				p = &a[n_a - (++n_rev)];
+				p->x = 1ULL << 63 | (r & 0xffffffff00000000ULL) | rpos;
+				p->y = (uint64_t)q->q_span << 32 | (uint32_t)(qlen - (int)((q->q_pos >> 1) + 1 - q->q_span) - 1);
+			}
+			if (q->is_tandem) p->y |= 1ULL << 42;                                  // MM_SEED_TANDEM
+			if (is_self) p->y |= 1ULL << 43;                                       // MM_SEED_SELF
+		}
+		if ((uint32_t)heap[0].y < q->n - 1) {
+			++heap[0].y;
+			heap[0].x = m[heap[0].y >> 32].cr[(uint32_t)heap[0].y];
+		} else {
+			heap[0] = heap[heap_size - 1];
+			--heap_size;
+		}
+		ks_heapdown_heap(0, heap_size, heap.data());
+	}
+	for (int64_t j = 0; j < n_rev >> 1; ++j) std::swap(a[n_a - 1 - j], a[n_a - (n_rev - j)]);      // :210-214
+	if (n_a > n_for + n_rev) {                                                     // :215-218
+		memmove(a + n_for, a + n_a - n_rev, (size_t)n_rev * sizeof(m128));
+		n_a = n_for + n_rev;
+	}
+	return n_a;
+}
+
 uint64_t hash64_masked(uint64_t key, uint64_t mask)
 {
 	key = (~key + (key << 21)) & mask;

@@ -93,6 +93,26 @@ void radix_sort_128x(m128 *beg, m128 *end);
 void radix_sort_128x_parallel(m128 *beg, m128 *end, int n_threads);
 void radix_sort_64(uint64_t *beg, uint64_t *end);
 
+// ---- collect_seed_hits_heap, src/map.c:156-220 (MM_F_HEAP_SORT, --heap-sort=yes): the seeds of one query merged through a binary heap ----
+// The device serves the flag at every job size (csrc/window_kernel.h: heap_order_block); this is the same algorithm in plain C++. No code path of the library
+// calls it — no hand-over of tied jobs to the host was built — it is kept beside radix_sort_128x as the restatement the emulator tests check the kernels against
+// (tests/simt_emu/emu_heapseed.cpp).
+struct HeapMatch {                                                    // mm_match_t, src/map.c:90-95
+	uint32_t n, q_pos, q_span;                                        // occurrences (below the cut-off), the minimizer's pos << 1 | strand, its span
+	bool is_tandem;
+	const uint64_t *cr;                                               // the key's positions: strictly ascending (src/index.c:239)
+};
+struct SeedSkip {                                                     // what skip_seed (src/map.c:132-154) looks at, the name comparison as the device sees it (wm_names.h)
+	int64_t flag = 0;                                                 // F_NO_DIAG | F_NO_DUAL (read only with a key) | F_FOR_ONLY | F_REV_ONLY
+	bool has_key = false; uint32_t q_lo = 0; int q_eq = 0;
+	const uint32_t *name_rank = 0, *seq_len = 0;                      // per contig
+};
+bool skip_seed(const SeedSkip &k, uint64_t r, uint32_t q_pos, int qlen, bool *is_self);
+void ks_heapdown_heap(size_t i, size_t n, m128 *l);                   // src/ksort.h:43-53 with heap_lt(a, b) = a.x > b.x (src/map.c:87-88)
+void ks_heapmake_heap(size_t n, m128 *l);                             // src/ksort.h:54-59
+// a: room for n_a = sum of m[i].n anchors; returns how many skip_seed kept (a[0 .. that) is the list handed to mm_chain_dp)
+int64_t seed_hits_heap(const HeapMatch *m, int n_m, int64_t n_a, int qlen, const SeedSkip &k, m128 *a);
+
 // ---- hashing, src/sketch.c:43-63 and khash.h Wang / X31 used for the per-read tie-break hash (src/map.c:355-357) ----
 uint64_t hash64_masked(uint64_t key, uint64_t mask);
 uint64_t hash64_full(uint64_t key);                                   // src/hit.c:40-50

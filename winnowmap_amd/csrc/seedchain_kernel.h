@@ -4,7 +4,8 @@
 //                position run), drop over-represented minimizers (occ >= mid_occ, accumulating rep_len exactly as
 //                collect_matches does), mark tandem seeds, and expand to anchors in minimizer order with a wave
 //                prefix sum. The unstable radix_sort_128x that follows in the reference is applied by the caller
-//                (its tie permutation is inherently sequential).
+//                (its tie permutation is inherently sequential). With MM_F_HEAP_SORT the anchors
+//                go into the order of collect_seed_hits_heap instead, on the device (window_kernel.h: heap_order_block).
 //  chain_wave  : mm_chain_dp's score fill. Anchor i is processed sequentially (f[i] depends on earlier f), but its
 //                predecessor scan j = i-1 … st runs 64 at a time: every lane scores one j (integer + the reference's
 //                fp64 gap cost), the "t[] marks" are scattered and re-read (marks only flow from larger to smaller
@@ -49,7 +50,7 @@ WM_DEV vbool seed_skip(const wm_index_view_t &ix, int flag, uint32_t q_lo, int q
 }
 
 WM_DEV void seed_wave(const wm_index_view_t ix, const wm_seed_job_t jb, const wm128_t *mini_pool, wm128_t *anchor_pool,
-                      int *occ_scratch /* n_mini ints */, wm_seed_res_t *res)
+                      int *occ_scratch /* n_mini ints */, wm_seed_res_t *res, uint32_t *first_scratch = 0 /* n_mini: every minimizer's first position, kept for the heap order (MM_F_HEAP_SORT) */)
 {
 	const V<int> ln = lane();
 	const uint64_t *mini = (const uint64_t*)(mini_pool + jb.mini_off);
@@ -79,6 +80,7 @@ WM_DEV void seed_wave(const wm_index_view_t ix, const wm_seed_job_t jb, const wm
 				WM_END
 			}
 			cst(occ_scratch, m, cnt);
+			if (first_scratch) gst(first_scratch, m, cast<uint32_t>(first));
 		WM_END
 		// occurrence filter + (optional) strand filter decide how many anchors each minimizer contributes
 		V<int> emit = sel(have && cnt < jb.max_occ, cnt, 0);

@@ -632,4 +632,219 @@ WM_DEV void win_small_wave(const wm_win_job_t jb, int n, const wm128_t *ga_, uns
 	win_extract_wave<false>(n, jb.min_cnt, jb.min_sc, stage, sf, sp, lv, lt, zu, b, wb, ws, res, u_pool, v_pool, pool_ctr);
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// MM_F_HEAP_SORT (--heap-sort=yes): collect_seed_hits_heap (src/map.c:156-220) instead of collect_seed_hits + radix_sort_128x. The heap pops the
+// occurrences in ascending order of the index value r, forward anchors are laid down from the front and reverse ones from the back (then reversed):
+// the list comes out sorted by x, and whenever the x of a job are distinct it is THE sorted list — what the sort machinery above gives as well.
+// Only inside a group of equal x (two query minimizers of one key and strand on one reference position) does the order belong to the heap:
+// ks_heapdown (src/ksort.h:43-53) prefers the left child on ties and sinks past equal keys, so the order depends on the heap's whole history.
+// heap_order_block therefore sorts the seeded anchors with the workgroup's stable LSD passes (win_bigsort_block: parallel at every size, its tie flag says
+// whether two x are equal), and only a job that has equal x replays the heap literally (heap_replay_wave, one wavefront):
+//   build    the matches with at least one occurrence, in minimizer order (:169-175), wave-parallel; entry = (r, minimizer << 32 | occurrence)
+//   make     ks_heapmake (src/ksort.h:54-59), lane 0
+//   pop      64 pops at a time by lane 0 (:177-205 without the anchor), recorded in LDS; then the wave turns the 64 records into anchors with the
+//            seeding's own skip test (seed_skip) and places them: forward from the front, reverse from the back (:183-195)
+//   finish   the reverse part is reversed (:210-214); the region holds exactly the anchors skip_seed keeps (the seed kernel counted them with the
+//            same test), so the closing-up of :215-218 has nothing to move — a count that does not match is a malformed job (returns 3).
+// The heap (16 B per entry, at most n_mini entries) lives in LDS where it fits (hcap entries at hl), in the job's global scratch (hg) otherwise.
+// Every loop is bounded: a heapdown halves its range, the pops are counted against the occurrences that entered the heap.
+// WM_HEAP_EVENT(k): 0 = a job kept its sorted list (no equal x), 1 = a job replayed the heap, 2 = the heap lived in global memory (emulator tests).
+// ------------------------------------------------------------------------------------------------------------------------------
+#ifndef WM_HEAP_EVENT
+#define WM_HEAP_EVENT(k) ((void)0)
+#endif
+enum { WM_SEED_HEAP_BIT = 0x400000 };
+
+// ks_heapdown / ks_heapmake of KSORT_INIT(heap, mm128_t, heap_lt), heap_lt(a, b) = a.x > b.x (src/map.c:87-88, src/ksort.h:43-59); h = (x, y) pairs; lane 0
+WM_DEV void hp_heapdown(size_t i, size_t n, uint64_t *h)
+{
+	size_t k = i;
+	const uint64_t tx = h[2 * i], ty = h[2 * i + 1];
+	while ((k = (k << 1) + 1) < n) {
+		if (k != n - 1 && h[2 * k] > h[2 * (k + 1)]) ++k;
+		if (h[2 * k] > tx) break;
+		h[2 * i] = h[2 * k]; h[2 * i + 1] = h[2 * k + 1]; i = k;
+	}
+	h[2 * i] = tx; h[2 * i + 1] = ty;
+}
+WM_DEV void hp_heapmake(size_t n, uint64_t *h)
+{
+	for (size_t i = (n >> 1) - 1; i != (size_t)-1; --i) hp_heapdown(i, n, h);
+}
+// up to 64 pops (src/map.c:177-180, 196-204): rec[2 q], rec[2 q + 1] = the popped (r, minimizer << 32 | occurrence); io[0] = heap size (in / out), io[1] = pops made
+WM_DEV void hp_pop64(uint64_t *h, const uint64_t *P, const int *occ, const uint32_t *first, uint64_t *rec, int *io)
+{
+	int n = io[0], q = 0;
+	while (n > 0 && q < 64) {
+		const uint64_t y = h[1];
+		rec[2 * q] = h[0]; rec[2 * q + 1] = y; ++q;
+		const uint32_t mi = (uint32_t)(y >> 32), o = (uint32_t)y;
+		if (o < (uint32_t)occ[mi] - 1u) { h[1] = y + 1; h[0] = P[(uint64_t)first[mi] + o + 1]; }
+		else { h[0] = h[2 * (size_t)(n - 1)]; h[1] = h[2 * (size_t)(n - 1) + 1]; --n; }
+		hp_heapdown(0, (size_t)n, h);
+	}
+	io[0] = n; io[1] = q;
+}
+
+// the literal replay: S[0 .. m) receives the job's seeded anchors in the heap's order. occ / first: count and first position of every minimizer as the
+// seed kernel cached them. ws: at least 264 ints of LDS. Returns 0, or 3 = the job is malformed (counts that contradict the seed kernel's)
+WM_DEV int heap_replay_wave(const wm_index_view_t ix, int filt, uint32_t q_lo, int q_eq, int qlen, int max_occ, const wm128_t *mini_, int n_mini,
+                            const int *occ, const uint32_t *first, wm128_t *S_, int m, uint64_t *hl, int hcap, uint64_t *hg, int *ws)
+{
+	const V<int> ln = lane();
+	const uint64_t *mini = (const uint64_t*)mini_;
+	uint64_t *S = (uint64_t*)S_;
+	WM_HEAP_EVENT(1);
+	// how many matches enter the heap, how many pops they make
+	int n_heap = 0;
+	long long n_pop = 0;
+	for (int m0 = 0; m0 < n_mini; m0 += 64) {
+		const V<int> mi = ln + m0;
+		V<int> cnt = 0;
+		WM_IF(mi < n_mini) cnt = gld(occ, mi); WM_END
+		cnt = sel(cnt < max_occ, cnt, V<int>(0));
+		n_heap += popc64(ballot(cnt > 0));
+		n_pop += (long long)readlane(wave_sum_i32(cnt), 0);
+	}
+	if (n_pop < (long long)m) return 3;
+	uint64_t *h = n_heap <= hcap ? hl : hg;
+	if (n_heap > hcap) WM_HEAP_EVENT(2);
+	{
+		int base = 0;
+		for (int m0 = 0; m0 < n_mini; m0 += 64) {                               // src/map.c:169-175
+			const V<int> mi = ln + m0;
+			V<int> cnt = 0;
+			WM_IF(mi < n_mini) cnt = gld(occ, mi); WM_END
+			const vbool in = cnt > 0 && cnt < max_occ;
+			const uint64_t em = ballot(in);
+			WM_IF(in)
+				const V<long long> slot = cast<long long>(mbcnt(em) + base);
+				gst(h, slot * 2LL, gld(ix.P, cast<uint64_t>(gld(first, mi))));
+				gst(h, slot * 2LL + 1LL, cast<uint64_t>(cast<uint32_t>(mi)) << 32);
+			WM_END
+			base += popc64(em);
+		}
+	}
+	win_fence();
+	uint64_t *rec = (uint64_t*)ws;
+	int *io = ws + 256;
+	WM_LANE0_BEGIN hp_heapmake((size_t)n_heap, h); io[0] = n_heap; io[1] = 0; WM_LANE0_END
+	int n_for = 0, n_rev = 0;
+	long long popped = 0;
+	bool bad = false;
+	for (;;) {
+		win_fence();
+		WM_LANE0_BEGIN hp_pop64(h, ix.P, occ, first, rec, io); WM_LANE0_END
+		win_fence();
+		const int q = uniform(gld(io, 1LL));
+		if (q <= 0) break;
+		popped += q;
+		if (popped > n_pop) { bad = true; break; }                               // more pops than occurrences entered the heap: never on a well-formed job
+		const vbool have = ln < q;
+		V<uint64_t> r = (uint64_t)0, ry = (uint64_t)0, mx = (uint64_t)0, my = (uint64_t)0;
+		vbool tandem = ln != ln, keep = ln != ln, self = ln != ln;
+		WM_IF(have)
+			r = gld(rec, cast<long long>(ln) * 2LL); ry = gld(rec, cast<long long>(ln) * 2LL + 1LL);
+			const V<long long> mi = cast<long long>(ry >> 32);
+			mx = gld(mini, mi * 2LL); my = gld(mini, mi * 2LL + 1LL);
+			WM_IF(mi > 0LL) tandem = tandem || ((gld(mini, (mi - 1LL) * 2LL) >> 8) == (mx >> 8)); WM_END       // src/map.c:121-122
+			WM_IF(mi < (long long)(n_mini - 1)) tandem = tandem || ((gld(mini, (mi + 1LL) * 2LL) >> 8) == (mx >> 8)); WM_END
+			keep = ln == ln;
+			if (filt) keep = !seed_skip(ix, filt, q_lo, q_eq, qlen, r, cast<uint32_t>(my), self);            // :182
+		WM_END
+		const V<uint32_t> q_pos = cast<uint32_t>(my), q_span = cast<uint32_t>(mx & (uint64_t)0xff);
+		const vbool fwd = cast<uint32_t>(r & (uint64_t)1) == (q_pos & 1u);
+		const uint64_t bf = ballot(have && keep && fwd), br = ballot(have && keep && !fwd);
+		if (n_for + popc64(bf) + n_rev + popc64(br) > m) { bad = true; break; }
+		const V<uint64_t> rpos = (r & (uint64_t)0xffffffffu) >> 1;
+		V<uint64_t> ax = (r & (uint64_t)0xffffffff00000000ULL) | rpos;
+		V<uint64_t> ay = cast<uint64_t>(q_span) << 32;
+		V<int> w = mbcnt(bf) + n_for;                                             // :184
+		WM_IF(fwd) ay = ay | cast<uint64_t>(q_pos >> 1); WM_ELSE
+			ax = ax | ((uint64_t)1 << 63);
+			ay = ay | cast<uint64_t>(cast<uint32_t>(V<int>(qlen) - cast<int>((q_pos >> 1) + 1u - q_span) - 1));
+			w = V<int>(m - 1 - n_rev) - mbcnt(br);                                // :188
+		WM_END
+		ay = sel(tandem, ay | ((uint64_t)1 << 42), ay);
+		if (filt & 1) ay = sel(self, ay | ((uint64_t)1 << 43), ay);               // MM_SEED_SELF (:194)
+		WM_IF(have && keep) gst(S, cast<long long>(w) * 2LL, ax); gst(S, cast<long long>(w) * 2LL + 1LL, ay); WM_END
+		n_for += popc64(bf); n_rev += popc64(br);
+	}
+	if (bad || uniform(gld(io, 0LL)) != 0 || n_for + n_rev != m) return 3;
+	win_fence();
+	for (int j0 = 0; j0 < (n_rev >> 1); j0 += 64) {                               // :210-214
+		const V<int> j = ln + j0;
+		WM_IF(j < (n_rev >> 1))
+			const V<long long> hi = cast<long long>(V<int>(m - 1) - j) * 2LL, lo = cast<long long>(V<int>(m - n_rev) + j) * 2LL;
+			const V<uint64_t> hx = gld(S, hi), hy = gld(S, hi + 1LL), lx = gld(S, lo), ly = gld(S, lo + 1LL);
+			gst(S, hi, lx); gst(S, hi + 1LL, ly); gst(S, lo, hx); gst(S, lo + 1LL, hy);
+		WM_END
+	}
+	win_fence();
+	return 0;
+}
+
+// the seeded anchors S[0 .. m) of one job (global memory, in any order) into the order of collect_seed_hits_heap, by a workgroup of NWV wavefronts:
+// win_bigsort_block's stable LSD passes (b0 / b1: m anchors each, LDS or global memory) give the sorted list and say whether two x are equal. Without
+// equal x that list is the heap's and is copied back; with them wavefront 0 replays the heap (hl: hcap entries of LDS — b0 / b1 are free by then —,
+// hg: the job's global scratch). lds: WIN_HEAP_INTS(NWV) ints. Every wavefront of the workgroup calls this; returns (uniform) 0 / 3 as heap_replay_wave
+#define WIN_HEAP_INTS(NWV) (((WIN_BIG_INTS(NWV) + 3) & ~3) + 272)
+WM_DEV int heap_order_block(int NWV, const wm_index_view_t ix, int filt, uint32_t q_lo, int q_eq, int qlen, int max_occ, const wm128_t *mini, int n_mini,
+                            const int *occ, const uint32_t *first, wm128_t *S, int m, wm128_t *b0, wm128_t *b1, uint64_t *hl, int hcap, uint64_t *hg, int *lds)
+{
+	if (m <= 1) return 0;
+	const V<int> ln = lane();
+	const int wv = wave_in_block();
+	int tie = 0;
+	const int cur = win_bigsort_block(NWV, S, b0, b1, m, lds, &tie);
+	if (!tie) {
+		if (cur >= 0) {
+			const uint64_t *in = (const uint64_t*)(cur ? b1 : b0);
+			uint64_t *out = (uint64_t*)S;
+			for (int i0 = wv * 64; i0 < 2 * m; i0 += 64 * NWV) { const V<int> i = ln + i0; WM_IF(i < 2 * m) gst(out, i, gld(in, i)); WM_END }
+			win_fence();
+		}
+		if (wv == 0) WM_HEAP_EVENT(0);
+		return 0;
+	}
+	int *ws = lds + ((WIN_BIG_INTS(NWV) + 3) & ~3);                           // 264 ints for the replay, [270] its verdict for the other wavefronts
+	if (wv == 0) {
+		const int e = heap_replay_wave(ix, filt, q_lo, q_eq, qlen, max_occ, mini, n_mini, occ, first, S, m, hl, hcap, hg, ws);
+		ust(ws, 270, e);
+	}
+	block_sync_lds();
+	const int e = uniform(gld(ws, 270LL));
+	block_sync_lds();
+	return e;
+}
+
+// win_heap_kernel's job: a job that carries the bit, has a sequence and whose seeded part holds lo < m <= hi anchors gets that part ordered
+// (heap_order_block) and is then handed on as a job whose seeded anchors need no sort (src/map.c:811 has none): without handed-in anchors as a job
+// without a sequence (seq_off = -1: anchors chained as they are), with them as a job whose anchors all count as handed in (n_pre = n_a: only the
+// union sort of :833 runs, with the heap-ordered part as its input). The kernels that follow read the job and are the ones a call without the bit runs.
+// a: the job's anchors (n_pre handed-in ones, then the seeded ones). Returns (uniform) 0 / 3
+WM_DEV int win_heap_job(int NWV, const wm_index_view_t ix, wm_win_job_t *job, int n_a, int n_mini, int err, const wm128_t *mini, const int *occ, const uint32_t *first,
+                        wm128_t *a, wm128_t *b0, wm128_t *b1, uint64_t *hl, int hcap, uint64_t *hg, int lo, int hi, int *lds)
+{
+	const wm_win_job_t jb = *job;
+	if (!(jb.seed_flag & WM_SEED_HEAP_BIT) || jb.seq_off < 0 || n_a <= 0 || err) return 0;
+	const int n_pre = jb.n_pre < n_a ? jb.n_pre : n_a, m = n_a - n_pre;
+	if (m <= lo || m > hi) return 0;
+	const int e = heap_order_block(NWV, ix, jb.seed_flag & (0x100000 | 0x200000 | 3), jb.q_lo, jb.q_eq, jb.len, jb.max_occ, mini, n_mini, occ, first, a + n_pre, m, b0, b1, hl, hcap, hg, lds);
+	block_sync_lds();                                                         // (every wavefront has read the job)
+	if (e) return e;
+	if (wave_in_block() == 0) {
+		WM_LANE0_BEGIN if (n_pre > 0) job->n_pre = n_a; else job->seq_off = -1; WM_LANE0_END
+	}
+	return 0;
+}
+
+// seed_heap_kernel's job (wm_seed_batch*): the job's anchors, lo < m <= hi of them, into the heap's order. Returns (uniform) 0 / 3
+WM_DEV int seed_heap_job(int NWV, const wm_index_view_t ix, const wm_seed_job_t jb, int m, const wm128_t *mini, const int *occ, const uint32_t *first,
+                         wm128_t *a, wm128_t *b0, wm128_t *b1, uint64_t *hl, int hcap, uint64_t *hg, int lo, int hi, int *lds)
+{
+	if (m > jb.cap || m <= lo || m > hi) return 0;                            // (a slot that overflowed is left to the retry)
+	return heap_order_block(NWV, ix, jb.flag & (0x100000 | 0x200000 | 3), jb.q_lo, jb.q_eq, jb.qlen, jb.max_occ, mini, jb.n_mini, occ, first, a, m, b0, b1, hl, hcap, hg, lds);
+}
+
 } // namespace wmk

@@ -6,6 +6,7 @@
 #include "reads2bit.h"
 #include "sketch_kernel.h"
 #include "seedchain_kernel.h"
+#include "window_kernel.h"
 #include "host/wm_chain.h"
 
 
@@ -87,10 +88,29 @@ __global__ __launch_bounds__(64) void sketch_long_gather_kernel(const wm_sketch_
 }
 
 __global__ __launch_bounds__(64) void seed_kernel(wm_index_view_t ix, const wm_seed_job_t *jobs, const wm128_t *mini, wm128_t *anchors,
-                                                   int *occ_scratch, const uint64_t *occ_off, wm_seed_res_t *res)
+                                                   int *occ_scratch, const uint64_t *occ_off, wm_seed_res_t *res, uint32_t *first_scratch)
 {
 	const int j = blockIdx.x;
-	wmk::seed_wave(ix, jobs[j], mini, anchors, occ_scratch + occ_off[j], res + j);
+	wmk::seed_wave(ix, jobs[j], mini, anchors, occ_scratch + occ_off[j], res + j, first_scratch ? first_scratch + occ_off[j] : 0);
+}
+
+// MM_F_HEAP_SORT (launched only by a call that carries the bit, once per size class): every job's anchors, lo < m <= hi of them, from minimizer order into the
+// order of collect_seed_hits_heap (src/map.c:156-220; window_kernel.h: heap_order_block) — nothing is sorted on the host afterwards. lds_cap > 0: the sort's two
+// buffers and the heap live in LDS, 0: in buf0 / buf1 and gheap. *herr: 3 = a job's occurrence counts contradict its anchor count (the call fails)
+template <int NWV>
+__global__ __launch_bounds__(64 * NWV) void seed_heap_kernel(wm_index_view_t ix, const wm_seed_job_t *jobs, const wm128_t *mini, wm128_t *anchors, wm128_t *buf0, wm128_t *buf1, const int *occ_scratch,
+                                                              const uint32_t *first_scratch, const uint64_t *occ_off, const wm_seed_res_t *res, uint64_t *gheap, int lo, int hi, int lds_cap, int *herr)
+{
+	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+	int *lds = (int*)smem;
+	wm128_t *stage = (wm128_t*)(lds + WIN_HEAP_INTS(NWV));
+	const int j = blockIdx.x;
+	const wm_seed_job_t jb = jobs[j];
+	const bool in_lds = lds_cap > 0;
+	const int e = wmk::seed_heap_job(NWV, ix, jb, res[j].n_anchors, mini + jb.mini_off, occ_scratch + occ_off[j], first_scratch + occ_off[j], anchors + jb.out_off,
+	                                 in_lds ? stage : buf0 + jb.out_off, in_lds ? stage + lds_cap : buf1 + jb.out_off, in_lds ? (uint64_t*)stage : (uint64_t*)0, in_lds ? 2 * lds_cap : 0,
+	                                 gheap + 2 * occ_off[j], lo, hi, lds);
+	if (e && threadIdx.x == 0) atomicMax(herr, e);
 }
 
 // anchors of a seed batch as keys (x) / values (y) for the device sort; and back, with a per-job flag "two anchors share a key" (their
@@ -910,6 +930,12 @@ try {
 		wm128_t *d_mini = (wm128_t*)arena_take(c, (mini_total + 1) * sizeof(wm128_t));
 		wm128_t *d_out = (wm128_t*)arena_take(c, (tot + 1) * sizeof(wm128_t));
 		int *d_occ = (int*)arena_take(c, (occ_tot + 1) * 4);
+		const bool heap = (flag & wm::F_HEAP_SORT) != 0;      // --heap-sort=yes: first positions, heaps and sort buffers beyond LDS and one error word; allocated and launched only then
+		uint32_t *d_first = heap ? (uint32_t*)arena_take(c, (occ_tot + 1) * 4) : 0;
+		uint64_t *d_heap = heap ? (uint64_t*)arena_take(c, (occ_tot + 1) * 16) : 0;
+		int *d_herr = heap ? (int*)arena_take(c, 64) : 0;
+		wm128_t *d_hb0 = heap ? (wm128_t*)arena_take(c, (tot + 1) * sizeof(wm128_t)) : 0, *d_hb1 = heap ? (wm128_t*)arena_take(c, (tot + 1) * sizeof(wm128_t)) : 0;      // (the sort's ping-pong for jobs beyond LDS)
+		if (heap && (!d_first || !d_heap || !d_herr || !d_hb0 || !d_hb1)) return set_err(WM_ENOMEM, "seed batch does not fit the arena");
 		wm_seed_res_t *d_res = (wm_seed_res_t*)arena_take(c, jb.size() * sizeof(wm_seed_res_t) + 64);
 		if (!d_jobs || !d_occ_off || !d_mini || !d_out || !d_occ || !d_res) return set_err(WM_ENOMEM, "seed batch does not fit the arena");
 		HIPCHK(hipMemcpyAsync(d_jobs, jb.data(), jb.size() * sizeof(wm_seed_job_t), hipMemcpyHostToDevice, c->stream));
@@ -917,12 +943,27 @@ try {
 		HIPCHK(hipMemcpyAsync(d_mini, mini, mini_total * sizeof(wm128_t), hipMemcpyHostToDevice, c->stream));
 		wm_index_view_t ix = { c->d_hkey, c->d_hval, c->d_P, c->hbits, 0, c->d_name_rank, c->d_seq_len };
 		HIPCHK(hipEventRecord(c->ev[0], c->stream));
-		hipLaunchKernelGGL(seed_kernel, dim3((int)jb.size()), dim3(64), 0, c->stream, ix, d_jobs, d_mini, d_out, d_occ, d_occ_off, d_res);
+		hipLaunchKernelGGL(seed_kernel, dim3((int)jb.size()), dim3(64), 0, c->stream, ix, d_jobs, d_mini, d_out, d_occ, d_occ_off, d_res, d_first);
+		int herr = 0;
+		if (heap) {
+			constexpr int NWV = 8, kSmall = 256, kLarge = 4096;      // the window op's classes (wm_window.hip)
+			const int nj = (int)jb.size();
+			HIPCHK(hipMemsetAsync(d_herr, 0, 4, c->stream));
+			HIPCHK(hipFuncSetAttribute((const void*)seed_heap_kernel<NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+			hipLaunchKernelGGL(seed_heap_kernel<1>, dim3(nj), dim3(64), (size_t)WIN_HEAP_INTS(1) * 4 + (size_t)kSmall * 32, c->stream, ix, d_jobs, d_mini, d_out, d_hb0, d_hb1, d_occ, d_first,
+			                   d_occ_off, d_res, d_heap, -1, kSmall, kSmall, d_herr);
+			hipLaunchKernelGGL(seed_heap_kernel<NWV>, dim3(nj), dim3(64 * NWV), (size_t)WIN_HEAP_INTS(NWV) * 4 + (size_t)kLarge * 32, c->stream, ix, d_jobs, d_mini, d_out, d_hb0, d_hb1, d_occ, d_first,
+			                   d_occ_off, d_res, d_heap, kSmall, kLarge, kLarge, d_herr);
+			hipLaunchKernelGGL(seed_heap_kernel<NWV>, dim3(nj), dim3(64 * NWV), (size_t)WIN_HEAP_INTS(NWV) * 4, c->stream, ix, d_jobs, d_mini, d_out, d_hb0, d_hb1, d_occ, d_first,
+			                   d_occ_off, d_res, d_heap, kLarge, 0x7fffffff, 0, d_herr);
+		}
 		HIPCHK(hipEventRecord(c->ev[1], c->stream));
 		UBuf<wm_seed_res_t> res(jb.size() + 1, c);
 		HIPCHK(hipMemcpyAsync(res.data(), d_res, jb.size() * sizeof(wm_seed_res_t), hipMemcpyDeviceToHost, c->stream));
+		if (heap) HIPCHK(hipMemcpyAsync(&herr, d_herr, 4, hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(ctx_sync(c));
 		HIPCHK(hipGetLastError());
+		if (herr) return set_err(WM_EINTERNAL, "heap-ordered seeding: a job's occurrence counts contradict its anchor count");
 		float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1])); ms_total += ms;
 		std::vector<int> again;
 		std::vector<size_t> done_t;
@@ -939,6 +980,17 @@ try {
 		// permutation of the reference's in-place unstable radix sort, which is sequential by nature -> those jobs are re-sorted on the host.
 		// Opt-in (WM_SEED_DEVICE_SORT=1): on BASELINE config 2 the extra device pass + synchronisation costs about what the host sort on idle
 		// workers costs (0.165 vs 0.174 Gbp/s, profiles/r02x_bench_device_seed_sort.json); it pays when single jobs hold 10^5..10^6 anchors.
+		if (heap) {                                 // the device left every finished job in the heap's order (src/map.c:811: no sort follows)
+			UBuf<wm128_t> raw(tot + 1, c);
+			HIPCHK(hipMemcpyAsync(raw.data(), d_out, tot * sizeof(wm128_t), hipMemcpyDeviceToHost, c->stream));
+			HIPCHK(ctx_sync(c));
+			wm::parallel_for(c->host_threads, done_t.size(), [&](size_t k) {
+				const size_t t = done_t[k];
+				memcpy(out + out_off[todo[t]], raw.data() + jb[t].out_off, (size_t)res[t].n_anchors * sizeof(wm128_t));
+			});
+			todo.swap(again);
+			continue;
+		}
 		const bool host_sort = !(getenv("WM_SEED_DEVICE_SORT") && atoi(getenv("WM_SEED_DEVICE_SORT")) != 0);
 		UBuf<wm128_t> tmp(tot + 1, c);
 		UBuf<int> tie(jb.size() + 1, c);

@@ -155,6 +155,29 @@ __global__ __launch_bounds__(64) void win_seed_kernel(wm_index_view_t ix, const 
 	}
 }
 
+// MM_F_HEAP_SORT (launched only by a call that carries the bit, once per size class): the seeded anchors of every job with lo < m <= hi of them go from minimizer
+// order into the order of collect_seed_hits_heap (window_kernel.h: heap_order_block) — sorted by the workgroup's stable LSD passes, replayed through the heap when
+// two of them share x — and the job is handed on as one whose seeded part needs no sort (win_heap_job). lds_cap > 0: the sort's two buffers and the heap live in LDS
+// (2 * lds_cap anchors after the workspace); 0: in buf0 / buf1 and gheap. herr: a word of its own (3 = a job's occurrence counts contradict its anchor count)
+template <int NWV>
+__global__ __launch_bounds__(64 * NWV) void win_heap_kernel(wm_index_view_t ix, wm_win_job_t *jobs, const wm_sketch_job_t *__restrict__ sj, const wm128_t *__restrict__ mini_pool,
+                                                             const int *occ, const uint32_t *first, wm128_t *anchors, wm128_t *buf0, wm128_t *buf1, wm_win_res_t *res, uint64_t *gheap,
+                                                             int lo, int hi, int lds_cap, int *herr)
+{
+	WM_SETPRIO(2);
+	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+	int *lds = (int*)smem;
+	wm128_t *stage = (wm128_t*)(lds + WIN_HEAP_INTS(NWV));
+	const int j = blockIdx.x;
+	const wm_win_res_t r = res[j];
+	const wm_sketch_job_t s = sj[j];
+	const bool in_lds = lds_cap > 0;
+	const int e = wmk::win_heap_job(NWV, ix, jobs + j, r.n_a, r.n_mini, r.err, mini_pool + s.out_off, occ + s.out_off, first + s.out_off, anchors + r.a_off,
+	                                in_lds ? stage : buf0 + r.a_off, in_lds ? stage + lds_cap : buf1 + r.a_off, in_lds ? (uint64_t*)stage : (uint64_t*)0, in_lds ? 2 * lds_cap : 0,
+	                                gheap + 2 * s.out_off, lo, hi, lds);
+	if (e && threadIdx.x == 0) { res[j].err = e; atomicMax(herr, e); }
+}
+
 // jobs of at most WIN_SMALL anchors: sorts, fill and extraction by one wavefront in LDS (win_small_wave); larger ones take the kernels below
 __global__ __launch_bounds__(64) void win_small_kernel(const wm_win_job_t *__restrict__ jobs, wm_win_res_t *res, const wm128_t *__restrict__ anchors,
                                                         uint64_t *u_pool, wm128_t *v_pool, uint64_t *pool_ctr)
@@ -345,7 +368,7 @@ int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t
 		    (s.seq_off == -1 && s.stage_off + (uint64_t)s.len > seqs_bytes)) { if (bad < 0) bad = i; }
 		d.seq_off = has_seq ? 0 : -1; d.pre_off = s.pre_off; d.len = s.len; d.n_pre = s.n_pre; d.max_occ = max_occ;
 		// (the name bits travel only with a key: skip_seed with qname == NULL ignores them, src/map.c:135)
-		d.seed_flag = (int32_t)(flag & (0x100000 | 0x200000 | (keys && c->d_name_rank ? 3 : 0))); d.q_lo = keys ? keys[i].lo : 0; d.q_eq = keys ? (int32_t)keys[i].eq : 0;
+		d.seed_flag = (int32_t)(flag & (0x100000 | 0x200000 | 0x400000 | (keys && c->d_name_rank ? 3 : 0))); d.q_lo = keys ? keys[i].lo : 0; d.q_eq = keys ? (int32_t)keys[i].eq : 0;
 		d.max_dist_x = s.par.max_dist_x; d.min_dist_x = s.par.min_dist_x; d.max_dist_y = s.par.max_dist_y; d.bw = s.par.bw; d.max_skip = s.par.max_skip; d.max_iter = s.par.max_iter;
 		d.min_cnt = s.par.min_cnt; d.min_sc = s.par.min_sc; d.gap_scale = s.par.gap_scale; d.is_cdna = s.par.is_cdna != 0;
 		wm_sketch_job_t &k = sj[i];
@@ -382,7 +405,10 @@ int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t
 	if (ties_on_host && !d_tie) return set_err(WM_ENOMEM, "window batch does not fit the arena");
 	int *d_dstat = sdust_thres > 0 ? (int*)arena_take(c, (size_t)(2 + (size_t)n) * 4 + 64) : 0;      // -T: win_dust_kernel's counters and list
 	if (sdust_thres > 0 && !d_dstat) return set_err(WM_ENOMEM, "window batch does not fit the arena");
-	uint64_t *d_ctr = (uint64_t*)arena_take(c, 64);          // [0] anchors used, [1] chains in the result pool, [2] anchors in the result pool, [3] worst err (int), [4..5] the four class counts (ints)
+	const bool heap = (flag & wm::F_HEAP_SORT) != 0;                      // --heap-sort=yes: one more scratch array (the heaps that do not fit LDS) and win_heap_kernel, only then
+	uint64_t *d_heap = heap ? (uint64_t*)arena_take(c, (mtot + 1) * 16) : 0;
+	if (heap && !d_heap) return set_err(WM_ENOMEM, "window batch does not fit the arena");
+	uint64_t *d_ctr = (uint64_t*)arena_take(c, 64);          // [0] anchors used, [1] chains in the result pool, [2] anchors in the result pool, [3] worst err (int; the int above it: the heap order's own error, MM_F_HEAP_SORT), [4..5] the four class counts (ints)
 	if (!d_jobs || !d_sj || !d_ord || !d_seqs || !d_pre || !d_so || !d_sx || !d_sy || !d_sl || !d_mini || !d_mcnt || !d_occ || !d_emit || !d_first || !D.d_res || !d_cj || !d_lists || !d_ctr)
 		return set_err(WM_ENOMEM, "window batch does not fit the arena");
 	int *d_counts = (int*)(d_ctr + 4);
@@ -419,6 +445,17 @@ int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t
 	hipLaunchKernelGGL(win_seed_kernel, dim3(n), dim3(64), 0, c->stream, ix, d_jobs, d_sj, d_mcnt, d_mini, d_pre, d_occ, d_first, d_emit, d_a, d_ctr, cap, D.d_res, (int*)(d_ctr + 3));
 	const size_t ws_bytes = (size_t)wmk::WIN_WS_PAD * 4;
 	static const int kSmall = wmk::WIN_SMALL, kLarge = 4096;
+	if (heap) {      // three size classes of the seeded part, LDS sized per class: the bulk by one wavefront, up to kLarge by a workgroup in LDS, beyond it in global memory
+		constexpr int NWV = 8;
+		int *d_herr = (int*)(d_ctr + 3) + 1;
+		HIPCHK(hipFuncSetAttribute((const void*)win_heap_kernel<NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+		hipLaunchKernelGGL(win_heap_kernel<1>, dim3(n), dim3(64), (size_t)WIN_HEAP_INTS(1) * 4 + (size_t)kSmall * 32, c->stream, ix, d_jobs, d_sj, d_mini, d_occ, d_first, d_a, d_b, d_w, D.d_res,
+		                   d_heap, -1, kSmall, kSmall, d_herr);
+		hipLaunchKernelGGL(win_heap_kernel<NWV>, dim3(n), dim3(64 * NWV), (size_t)WIN_HEAP_INTS(NWV) * 4 + (size_t)kLarge * 32, c->stream, ix, d_jobs, d_sj, d_mini, d_occ, d_first, d_a, d_b, d_w, D.d_res,
+		                   d_heap, kSmall, kLarge, kLarge, d_herr);
+		hipLaunchKernelGGL(win_heap_kernel<NWV>, dim3(n), dim3(64 * NWV), (size_t)WIN_HEAP_INTS(NWV) * 4, c->stream, ix, d_jobs, d_sj, d_mini, d_occ, d_first, d_a, d_b, d_w, D.d_res,
+		                   d_heap, kLarge, 0x7fffffff, 0, d_herr);
+	}
 	// the bulk (jobs of at most WIN_SMALL anchors: one MCAS window yields ~100) finishes in one kernel; the rest goes class by class
 	HIPCHK(hipFuncSetAttribute((const void*)win_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 	hipLaunchKernelGGL(win_small_kernel, dim3(n), dim3(64), (size_t)wmk::WIN_SMALL_LDS, c->stream, d_jobs, D.d_res, d_a, D.d_upool, D.d_vpool, d_ctr + 1);
@@ -515,6 +552,7 @@ int window_fetch(wm_ctx_t *c, const WinDev &D, int n, wm_window_res_t *res, uint
 int window_verdict(const WinDev &D, int round)
 {
 	if (D.tot[2] == 2) return set_err(WM_ENOMEM, "window batch does not fit the arena (anchor pool)");
+	if (D.ctr[3] >> 32) return set_err(WM_EINTERNAL, "heap-ordered seeding: a job's occurrence counts contradict its anchor count");
 	if (D.tot[2] == 1) return round == 0 ? 1 : set_err(WM_EINTERNAL, "minimizer slot overflow at full size");
 	return 0;
 }

@@ -587,6 +587,9 @@ MM_F_CIGAR, MM_F_OUT_SAM, MM_F_OUT_CG = 0x4, 0x8, 0x20
 # self / all-vs-all mapping (src/minimap.h:9-31, skip_seed src/map.c:132-154): -D, --dual=no, -P, --no-long-join; -X is all four (src/main.c)
 MM_F_NO_DIAG, MM_F_NO_DUAL, MM_F_NO_LJOIN, MM_F_ALL_CHAINS = 0x1, 0x2, 0x400, 0x800000
 MM_F_AVA = MM_F_ALL_CHAINS | MM_F_NO_DIAG | MM_F_NO_DUAL | MM_F_NO_LJOIN
+# --heap-sort=yes (src/main.c:261-262): the seeds of a query merged through a binary heap (collect_seed_hits_heap, src/map.c:156-220) instead of collected and
+# radix-sorted; the two orders differ where two anchors share x. Served by the seeding and window operations and by the mapper
+MM_F_HEAP_SORT = 0x400000
 STAT_NAMES = ("super_steps", "ksw_jobs", "chain_jobs", "seed_jobs", "sketch_jobs", "dp_cells", "ksw_kernel_us", "aux_kernel_us", "read_bases")
 
 

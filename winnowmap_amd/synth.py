@@ -101,6 +101,25 @@ def make_reads(contigs, n_reads, read_len, seed, profile="ont", sv_frac=0.0):
     return reads, truth
 
 
+def make_dup_reads(contigs, n_reads, seed, host=(2000, 6000), unit=(60, 800), copies=(2, 5)):
+    """Reads that carry a tandem duplication INSIDE the read: a stretch of `host` bases of a contig in which a unit of `unit` bases is repeated `copies`
+    times in place (ranges inclusive), a third of the reads each exact / hifi / ont (PROFILES), every second one reverse-complemented. Two minimizers of
+    such a read share key and strand and hit the same reference position: anchors of equal x, which --heap-sort=yes and the radix path order differently."""
+    rng = np.random.default_rng(seed)
+    reads = []
+    for i in range(n_reads):
+        c = contigs[int(rng.integers(0, len(contigs)))]
+        hl = int(rng.integers(host[0], host[1] + 1))
+        st = int(rng.integers(0, len(c) - hl))
+        ul = int(round(np.exp(rng.uniform(np.log(unit[0]), np.log(unit[1])))))      # log-uniform: short units are what real tandem duplications mostly are
+        up = int(rng.integers(0, hl - ul))
+        h = mutate_codes(c[st:st + hl], rng, *PROFILES[("exact", "hifi", "ont")[i % 3]])      # the errors first: the copies inside the read are identical
+        up = min(up, max(0, len(h) - ul))
+        r = np.concatenate([h[:up]] + [h[up:up + ul]] * int(rng.integers(copies[0], copies[1] + 1)) + [h[up + ul:]])
+        reads.append(np.ascontiguousarray(revcomp_codes(r) if (i // 3) % 2 else r))
+    return reads
+
+
 def codes_to_ascii(c):
     return _ACGT[c].tobytes()
 
