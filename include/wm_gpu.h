@@ -187,15 +187,18 @@ int wm_index_build(const char *fasta, const char *kmer_file, int k, int w, int n
  * builds the bloom filter before; the key table (src/index.c:200-252: per-bucket sort + hash fill) is built on the device as well — radix sort of
  * the minimizers, run-length encode, sort by home slot, linear probing as a prefix maximum (index_table_on_device) — with the host's builder as the
  * fall-back when the arena is too small for the sort. Bit-identical to wm_index_build (tests/test_aux_gpu.py).
- * Needs odd k (every preset); contigs are sketched in groups that fit the context's arena (~26 B per base). stats (optional, 4 doubles):
+ * Any k from 2 to 28; contigs are sketched in groups that fit the context's arena (~26 B per base; an even k adds 5 B per base: the steps that survive the
+ * palindrome rule of src/sketch.c:166, and keeps every contig on one wavefront, as -H does — see below). stats (optional, 4 doubles):
  * seconds reading + packing, sketching on the device (incl. transfers), building the table; minimizers. */
 int wm_index_build_gpu(wm_ctx_t *ctx, const char *fasta, const char *kmer_file, int k, int w, int n_threads, wm_index_t **out, double *stats);
 /* Both with the index flags of mm_idxopt_t::flag (src/minimap.h:41-43). Known here: MM_I_HPC = 1, the CLI's -H — minimizers over the homopolymer-
  * compressed sequence (src/sketch.c:152-163: a run of one base is one step, a minimizer sits on the last base of its last run and carries the summed length
- * of its k runs as span); a mapper on such an index sketches its reads the same way (the device sketch compacts every sequence into its runs first, needs
- * an odd k) and anchors are moved to the start of their runs before alignment (mm_adjust_minier, src/align.c:352-361). An index loaded from a file carries
+ * of its k runs as span); a mapper on such an index sketches its reads the same way (the device sketch compacts every sequence into its runs first; with an
+ * even k the runs whose k-mer is its own reverse complement are then taken out, src/sketch.c:160-166) and anchors are moved to the start of their runs before alignment (mm_adjust_minier, src/align.c:352-361). An index loaded from a file carries
  * its flag in the header. With -H the device build keeps every contig on ONE wavefront (the chunked sketch cuts in base space, the runs would have to be cut in
- * run space): for references with contigs of tens of Mb the host build (parallel per contig) is the faster of the two. */
+ * run space): for references with contigs of tens of Mb the host build (parallel per contig) is the faster of the two. The same holds for an even k, with or
+ * without -H: a k-mer that equals its reverse complement skips the whole step of the winnowing automaton (src/sketch.c:166), the ring then runs over the
+ * surviving steps, and sequences of WM_SKETCH_LONG codes and more stay on one wavefront — cutting chunks in step space is not done. */
 int wm_index_build_flag(const char *fasta, const char *kmer_file, int k, int w, int idx_flag, int n_threads, wm_index_t **out);
 int wm_index_build_gpu_flag(wm_ctx_t *ctx, const char *fasta, const char *kmer_file, int k, int w, int idx_flag, int n_threads, wm_index_t **out, double *stats);
 void wm_index_destroy(wm_index_t *idx);
@@ -234,7 +237,8 @@ int wm_index_import(const uint64_t *sizes9, const uint32_t *S, const uint64_t *h
                     const uint64_t *seq_meta, const char *names, wm_index_t **out);
 
 /* ---- sketch / seed / chain, batched (need wm_index_upload first) ------------------------------------ */
-/* mm_sketch of n sequences of 0..4 codes (rid = 0). Minimizers of sequence i: out[out_off[i] .. +counts[i]). */
+/* mm_sketch of n sequences of 0..4 codes (rid = 0). Minimizers of sequence i: out[out_off[i] .. +counts[i]). k = 2 .. 28, odd or even, one wavefront per
+ * sequence (WM_SKETCH_LANE=1 in the environment: the one-lane-per-sequence kernel, for A/B comparison; k = 1 always runs on it). */
 int wm_sketch_batch(wm_ctx_t *ctx, int n, const uint8_t *seqs, size_t seqs_bytes, const uint64_t *seq_off, const int32_t *len,
                     wm128_t *out, size_t out_cap, uint64_t *out_off, int32_t *counts);
 /* wm_sketch_batch without an index on the context: the caller supplies the -W bloom filter (the bit table and hash salts of the reference's
@@ -325,9 +329,16 @@ float wm_last_aux_ms(const wm_ctx_t *ctx);
  * A program that uses only the batched operations above is not touched by the second. */
 typedef struct wm_mapper_s wm_mapper_t;
 /* preset: NULL/"" or "map-ont" | "map-pb" | "map-pb-clr" | "asm5" | "asm10" | "asm20" (mm_set_opt, src/options.c:89);
- * flag: mm_mapopt_t::flag bits to OR in (MM_F_CIGAR 0x4, MM_F_OUT_SAM 0x8, MM_F_OUT_CG 0x20, ...). */
+ * flag: mm_mapopt_t::flag bits to OR in (MM_F_CIGAR 0x4, MM_F_OUT_SAM 0x8, MM_F_OUT_CG 0x20, ...).
+ * An index with an even k is refused (WM_EINVAL, "... needs an odd k ...") unless the process has switched even k on — see wm_set_even_k. */
 int wm_mapper_create(wm_ctx_t *ctx, const wm_index_t *idx, const char *preset, int64_t flag, wm_mapper_t **out);
 void wm_mapper_destroy(wm_mapper_t *m);
+/* Even k (the reference maps with any k <= 28, src/sketch.c:140; every preset has an odd one). The batched operations and the index builds serve it as
+ * they serve an odd k. The mapper — wm_mapper_create, wm_mapper_create_opt, the parts of wm_split_begin / wm_split_add_part and of
+ * wm_map_file_split_fasta — serves it only when the process has opted in: on = 1 from here, or WM_EVEN_K=1 in the environment, which is read whenever a
+ * mapper is made; on = 0: refused whatever the environment says; on < 0: back to the environment. Off by default. wm_even_k_enabled(): the current answer. */
+void wm_set_even_k(int on);
+int wm_even_k_enabled(void);
 /* host parallelism (the reference's -t): n_threads host threads run the per-read glue; they are organised in groups
  * (4 from 16 threads up, else 2 from 8 up; env WM_GROUPS) that each share one device batch per operation on their own HIP stream + arena slice
  * (arena_bytes_per_group; 0 = same size as ctx). */

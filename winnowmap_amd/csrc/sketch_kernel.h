@@ -172,7 +172,7 @@ WM_DEV void sketch_wave(const wm_sketch_params_t P, const wm_sketch_job_t *jobs,
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// sketch_coop: ONE WAVEFRONT per sequence, for odd k (every preset: k = 15 / 19). With k odd a k-mer never equals its reverse
+// sketch_coop: ONE WAVEFRONT per sequence. First for odd k (every preset: k = 15 / 19; even k: sketch_even_steps below). With k odd a k-mer never equals its reverse
 // complement, so the reference's "skip the palindrome" step (src/sketch.c:166) never fires, slot t of the winnowing ring is simply
 // position t, and a k-mer is valid iff the last k bases are all unambiguous (l >= k; an N only resets l, src/sketch.c:175).
 //
@@ -203,9 +203,12 @@ WM_DEV void sketch_wave(const wm_sketch_params_t P, const wm_sketch_job_t *jobs,
 // where the k bases that end at a position are one shifted 64-bit window instead of k byte loads
 // HPC: the "sequence" is the list of the automaton's steps (sketch_hpc_steps: seqs[s] = the code of step s, he[s] = the position of its last base):
 // a k-mer's position is he[s], its span he[s] - he[s - k] — the k runs are contiguous — and k-mers that span 256 bases or more are not used (:168)
-template <bool PACKED, bool HPC = false>
+// EVEN (even k, sketch_even_steps): the range is one of SURVIVING steps, ei[u] = the position (HPC: the run) of surviving step u. Everything a step
+// owns — its code, its k-mer, its end position, its span — is read at ei[u]; l counts surviving steps since the last ambiguous one (src/sketch.c:168), and
+// the slot is u. A step with l >= k has k unambiguous steps right behind ei[u], skipped ones included, so its k-mer is the plain window that ends there.
+template <bool PACKED, bool HPC = false, bool EVEN = false>
 WM_DEV void sketch_p1_range_t(const wm_sketch_params_t P, long long soff, int n, const uint8_t *seqs, const uint64_t *pk, const uint64_t *nm, const uint8_t *bloom_bits,
-                              double *so, uint64_t *sx, uint32_t *sy, uint32_t *sl, int begin, int end, const uint32_t *he = 0)
+                              double *so, uint64_t *sx, uint32_t *sy, uint32_t *sl, int begin, int end, const uint32_t *he = 0, const uint32_t *ei = 0)
 {
 	const int w = P.w, k = P.k;
 	const uint64_t mask = (1ULL << 2 * k) - 1;
@@ -231,19 +234,21 @@ WM_DEV void sketch_p1_range_t(const wm_sketch_params_t P, long long soff, int n,
 		const V<int> i = ln + t0;
 		const vbool in = i < end;
 		vbool amb = false;
+		V<int> a = i;                                // where the step's bases are: the slot itself, or (EVEN) the step that survived into it
 		WM_IF(in)
-			if constexpr (PACKED) amb = rd2_is_n(nm, cast<long long>(i) + soff); else amb = cast<int>(gld(seqs, cast<long long>(i) + soff)) >= 4;
+			if constexpr (EVEN) a = cast<int>(gld(ei, i));
+			if constexpr (PACKED) amb = rd2_is_n(nm, cast<long long>(a) + soff); else amb = cast<int>(gld(seqs, cast<long long>(a) + soff)) >= 4;
 		WM_END
 		const V<int> lastN = vmax(wave_scan_max(sel(in && amb, i, V<int>(-1))), last_n);
 		const V<int> l = i - lastN;                  // unambiguous bases ending here (0 on an N)
 		last_n = readlane(lastN, 63);
 		vbool valid = in && l >= k;
-		V<int> span = k, epos = i;
+		V<int> span = k, epos = a;
 		if constexpr (HPC) {
 			WM_IF(valid)
-				epos = cast<int>(gld(he, i));
+				epos = cast<int>(gld(he, a));
 				V<int> before = -1;
-				WM_IF(i >= k) before = cast<int>(gld(he, i - k)); WM_END
+				WM_IF(a >= k) before = cast<int>(gld(he, a - k)); WM_END
 				span = epos - before;
 			WM_END
 			valid = valid && span < 256;
@@ -254,12 +259,12 @@ WM_DEV void sketch_p1_range_t(const wm_sketch_params_t P, long long soff, int n,
 		WM_IF(valid)
 			V<uint64_t> f = (uint64_t)0, g = (uint64_t)0;
 			if constexpr (PACKED) {                  // the window of the k bases i-k+1 .. i, earliest base in the low bits: its complement IS the reverse-complement k-mer
-				const V<uint64_t> win = rd2_window(pk, cast<long long>(i - (k - 1)) + soff);
+				const V<uint64_t> win = rd2_window(pk, cast<long long>(a - (k - 1)) + soff);
 				g = ~win & mask;
 				f = rd2_rev(win) >> (64 - 2 * k);
 			} else {
 				for (int j = 0; j < k; ++j) {        // base j steps back: digit j of the forward k-mer, digit k-1-j of the reverse complement
-					const V<uint64_t> cj = cast<uint64_t>(gld(seqs, cast<long long>(i - j) + soff));
+					const V<uint64_t> cj = cast<uint64_t>(gld(seqs, cast<long long>(a - j) + soff));
 					f = f | (cj << (2 * j));
 					g = g | ((cj ^ (uint64_t)3) << (2 * (k - 1 - j)));
 				}
@@ -411,10 +416,95 @@ WM_DEV int sketch_hpc_steps(long long soff, int n, const uint8_t *seqs, const ui
 	return S;
 }
 
-// hc / he: scratch of jb.len entries each for the compacted sequence (P.hpc only)
-WM_DEV void sketch_coop(const wm_sketch_params_t P, const wm_sketch_job_t jb, const uint8_t *seqs, const uint64_t *pk, const uint64_t *nm, const uint8_t *bloom_bits,
-                        double *so, uint64_t *sx, uint32_t *sy, uint32_t *sl, wm128_t *out, int *count_out, uint8_t *hc = 0, uint32_t *he = 0)
+// ------------------------------------------------------------------------------------------------------------------------------
+// Even k: a k-mer may equal its reverse complement, and the reference then skips the WHOLE step (src/sketch.c:166): l is not incremented, the ring slot
+// is not written, buf_pos does not advance. The k-mer registers shift on every unambiguous base and an ambiguous one does not reset them (:164-165,
+// :175), so the test looks at the last k UNAMBIGUOUS codes, across N runs of any length, and can fire while l < k; before k unambiguous codes have been
+// read the zero padding of the two registers cannot match (the top digit of the forward register is 0 = A, which asks for a last base T, the low digit
+// of the reverse register is 0, which asks for a last base A). Under homopolymer compression the run is pushed to the queue of run lengths first
+// (:160-162): a skipped run still is one of the k runs of the k-mers after it.
+// So the automaton's steps are compacted once more into the steps that SURVIVE the test, and the two phases run over those: slot u of the ring is
+// surviving step u, l counts surviving steps. sketch_even_steps: pass 1 compacts the unambiguous codes (nn[r] = the r-th of them), pass 2 tests step a
+// against nn[r - k + 1 .. r] — k / 2 pairs of bytes — and lists the survivors in order with wave ballots: ei[u] = a. Returns their number.
+// seqs + soff / pk / nm: the n steps' codes as sk_code reads them (the sequence, or the homopolymer runs hc[] with soff = 0).
+// WM_EVENK_EVENT(skipped, low): how many steps a block of 64 skipped, and how many of those while l < k (emulator tests).
+// ------------------------------------------------------------------------------------------------------------------------------
+WM_DEV int sketch_even_steps(int k, long long soff, int n, const uint8_t *seqs, const uint64_t *pk, const uint64_t *nm, uint8_t *nn, uint32_t *ei)
 {
+	const V<int> ln = lane();
+	int R = 0;
+	for (int t0 = 0; t0 < n; t0 += 64) {
+		const V<int> i = ln + t0;
+		V<int> c = 4;
+		WM_IF(i < n) c = sk_code(seqs, pk, nm, V<long long>(soff), cast<long long>(i)); WM_END
+		const vbool base = c < 4;
+		const uint64_t bm = ballot(base);
+		WM_IF(base) gst(nn, mbcnt(bm) + R, cast<uint8_t>(c)); WM_END
+		R += popc64(bm);
+	}
+	mem_sync();
+	int U = 0;
+#ifdef WM_EVENK_EVENT
+	int last_nu = -1;                                // the surviving-step index of the last ambiguous step
+#endif
+	R = 0;
+	for (int t0 = 0; t0 < n; t0 += 64) {
+		const V<int> i = ln + t0;
+		const vbool in = i < n;
+		V<int> c = 4;
+		WM_IF(in) c = sk_code(seqs, pk, nm, V<long long>(soff), cast<long long>(i)); WM_END
+		const vbool base = c < 4;
+		const uint64_t bm = ballot(base);
+		const V<int> r = mbcnt(bm) + R;              // this step's code is nn[r]
+		vbool pal = base && r >= k - 1;
+		for (int j = 0; j < k / 2 && any(pal); ++j) {
+			WM_IF(pal) pal = cast<int>(gld(nn, r - j)) + cast<int>(gld(nn, r - (k - 1) + j)) == 3; WM_END
+		}
+		const vbool keep = in && !pal;
+		const uint64_t km = ballot(keep);
+		const V<int> u = mbcnt(km) + U;              // surviving steps before this one
+		WM_IF(keep) gst(ei, u, cast<uint32_t>(i)); WM_END
+#ifdef WM_EVENK_EVENT
+		{
+			const V<int> lastNu = vmax(wave_scan_max(sel(in && !base, u, V<int>(-1))), last_nu);
+			WM_EVENK_EVENT(popc64(ballot(pal)), popc64(ballot(pal && u - 1 - lastNu < k)));
+			last_nu = readlane(lastNu, 63);
+		}
+#endif
+		U += popc64(km);
+		R += popc64(bm);
+	}
+	return U;
+}
+
+// even k: hc / he as in sketch_coop, nn / ei = scratch of jb.len entries each (sketch_even_steps)
+WM_DEV void sketch_coop_even(const wm_sketch_params_t P, const wm_sketch_job_t jb, const uint8_t *seqs, const uint64_t *pk, const uint64_t *nm, const uint8_t *bloom_bits,
+                             double *so, uint64_t *sx, uint32_t *sy, uint32_t *sl, wm128_t *out, int *count_out, uint8_t *hc, uint32_t *he, uint8_t *nn, uint32_t *ei)
+{
+	const long long soff = (long long)jb.seq_off;
+	int U = 0;
+	if (P.hpc) {
+		const int S = sketch_hpc_steps(soff, jb.len, seqs, pk, nm, hc, he);
+		mem_sync();
+		U = sketch_even_steps(P.k, 0, S, hc, pk, nm, nn, ei);
+		mem_sync();
+		sketch_p1_range_t<false, true, true>(P, 0, U, hc, pk, nm, bloom_bits, so, sx, sy, sl, 0, U, he, ei);
+	} else {
+		U = sketch_even_steps(P.k, soff, jb.len, seqs, pk, nm, nn, ei);
+		mem_sync();
+		if (soff & (long long)WM_RD_PACKED_BIT) sketch_p1_range_t<true, false, true>(P, soff & (long long)(WM_RD_PACKED_BIT - 1), U, seqs, pk, nm, bloom_bits, so, sx, sy, sl, 0, U, 0, ei);
+		else sketch_p1_range_t<false, false, true>(P, soff, U, seqs, pk, nm, bloom_bits, so, sx, sy, sl, 0, U, 0, ei);
+	}
+	mem_sync();
+	const int n_out = sketch_p2_range(P, U, so, sx, sy, sl, 0, false, -1, out + jb.out_off, jb.cap);
+	WM_IF(lane() == 0) gst(count_out, V<long long>(0), V<int>(n_out)); WM_END
+}
+
+// hc / he: scratch of jb.len entries each for the compacted sequence (P.hpc only); nn / ei: the same for an even k (sketch_even_steps)
+WM_DEV void sketch_coop(const wm_sketch_params_t P, const wm_sketch_job_t jb, const uint8_t *seqs, const uint64_t *pk, const uint64_t *nm, const uint8_t *bloom_bits,
+                        double *so, uint64_t *sx, uint32_t *sy, uint32_t *sl, wm128_t *out, int *count_out, uint8_t *hc = 0, uint32_t *he = 0, uint8_t *nn = 0, uint32_t *ei = 0)
+{
+	if (!(P.k & 1)) { sketch_coop_even(P, jb, seqs, pk, nm, bloom_bits, so, sx, sy, sl, out, count_out, hc, he, nn, ei); return; }
 	if (P.hpc) {
 		const int S = sketch_hpc_steps((long long)jb.seq_off, jb.len, seqs, pk, nm, hc, he);
 		mem_sync();

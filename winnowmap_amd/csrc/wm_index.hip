@@ -20,17 +20,18 @@ __global__ __launch_bounds__(64) void sketch_kernel(wm_sketch_params_t P, const 
 	wmk::sketch_wave(P, jobs, n_jobs, blockIdx.x, seqs, rpk, rnm, bloom, ring_o, ring_y, out, counts);
 }
 
-// one wavefront per sequence (sketch_coop, odd k): order[] lists the jobs longest first; so / sx / sy / sl = per-position scratch
+// one wavefront per sequence (sketch_coop): order[] lists the jobs longest first; so / sx / sy / sl = per-position scratch
 __global__ __launch_bounds__(64) void sketch_coop_kernel(wm_sketch_params_t P, const wm_sketch_job_t *jobs, const int *order, const uint8_t *seqs, const uint64_t *rpk, const uint64_t *rnm,
                                                           const uint8_t *bloom, double *so, uint64_t *sx, uint32_t *sy, uint32_t *sl, wm128_t *out, int *counts, int long_thr,
-                                                          uint8_t *hc, uint32_t *he)
+                                                          uint8_t *hc, uint32_t *he, uint8_t *nn, uint32_t *ei)
 {
 	WM_SETPRIO(2);
 	const int j = order[blockIdx.x];
 	const wm_sketch_job_t jb = jobs[j];
 	if (long_thr > 0 && jb.len >= long_thr) return;           // sketched chunk by chunk (sketch_long_* kernels)
 	wmk::sketch_coop(P, jb, seqs, rpk, rnm, bloom, so + jb.scratch_off, sx + jb.scratch_off, sy + jb.scratch_off, sl + jb.scratch_off, out, counts + j,
-	                 hc ? hc + jb.scratch_off : 0, he ? he + jb.scratch_off : 0);        // (P.hpc: the job's compacted sequence)
+	                 hc ? hc + jb.scratch_off : 0, he ? he + jb.scratch_off : 0,         // (P.hpc: the job's compacted sequence)
+	                 nn ? nn + jb.scratch_off : 0, ei ? ei + jb.scratch_off : 0);        // (even k: its unambiguous codes and its surviving steps)
 }
 
 // ---- long sequences (contigs of the reference at index time, query contigs, stage-2 passes of very long reads): one wavefront per CHUNK of the
@@ -634,7 +635,7 @@ int wm_index_build_seqs_dev(wm_ctx_t *c, const wm::IdxOpt &io, std::vector<std::
 	const int k = io.k, w = io.w;
 	const char *kmer_file = kmer_file_s.c_str();
 	std::string err;
-	if (!(k & 1) || k < 2) return set_err(WM_EINVAL, "the device index build needs an odd k (got %d): use wm_index_build", k);
+	if (k < 2) return set_err(WM_EINVAL, "the device index build needs k >= 2 (got %d): use wm_index_build", k);
 	if (c->have_index && !replace_ok) return set_err(WM_EINVAL, "the context already holds an index: build on a fresh context, then wm_index_upload");
 	HIPCHK(hipSetDevice(c->device));
 	if (t0 < 0) t0 = now_ms();
@@ -659,7 +660,7 @@ int wm_index_build_seqs_dev(wm_ctx_t *c, const wm::IdxOpt &io, std::vector<std::
 	const size_t budget = (size_t)(c->arena_bytes * 0.85);
 	for (size_t g0 = 0; g0 < seqs.size() && rc == WM_OK;) {             // groups of contigs that fit the arena: 1 B codes + 24 B scratch + 2 B output + 4 B chunk-local output (+ tables) per base
 		size_t g1 = g0, bases = 0;
-		const size_t per_base = 34 + ((io.flag & 1) ? 5 : 0);             // (+ the homopolymer-compressed copy: a code and an end position per base)
+		const size_t per_base = 34 + ((io.flag & 1) ? 5 : 0) + (!(k & 1) ? 5 : 0);   // (+ the homopolymer-compressed copy: a code and an end position per base; + even k: an unambiguous code and a surviving step per base)
 		while (g1 < seqs.size() && (g1 == g0 || (bases + seqs[g1].size()) * per_base + 4096 * (g1 - g0 + 1) <= budget)) { bases += seqs[g1].size(); ++g1; }
 		if (bases * per_base > budget) { rc = set_err(WM_ENOMEM, "contig %zu (%zu bases) needs %.1f GB of arena for the device sketch", g0, seqs[g0].size(), seqs[g0].size() * per_base / 1073741824.0); break; }
 		const int n = (int)(g1 - g0);
@@ -723,9 +724,9 @@ extern "C" int wm_sketch_batch(wm_ctx_t *c, int n, const uint8_t *seqs, size_t s
 // The one-wavefront-per-sequence sketch of `n` jobs (h_jobs = the host copy of d_jobs) and, for sequences of WM_SKETCH_LONG (65 536) codes and more, the
 // chunked form: WM_SKETCH_CHUNK (16 384) positions per wavefront. allow_long = false (a repeat with full-size slots): everything on one wavefront each.
 // Everything is queued on the context's stream; with long jobs the call waits once (its chunk tables are staged in the pinned slab).
-static int sketch_long_thr(bool allow_long, int *chunk_out, bool hpc = false)
+static int sketch_long_thr(bool allow_long, int *chunk_out, bool hpc = false, bool even = false)
 {
-	if (hpc) { *chunk_out = 16384; return 0; }                 // homopolymer compression: every sequence on one wavefront (the chunks would have to be cut in run space)
+	if (hpc || even) { *chunk_out = 16384; return 0; }         // homopolymer compression, even k: every sequence on one wavefront (the chunks would have to be cut in run / step space)
 	static const int long_env = getenv("WM_SKETCH_LONG") ? atoi(getenv("WM_SKETCH_LONG")) : 65536;
 	static const int chunk = std::max(1024, getenv("WM_SKETCH_CHUNK") ? atoi(getenv("WM_SKETCH_CHUNK")) : 16384);
 	*chunk_out = chunk;
@@ -733,15 +734,15 @@ static int sketch_long_thr(bool allow_long, int *chunk_out, bool hpc = false)
 }
 // device bytes sketch_launch needs on top of the caller's buffers (chunk tables + chunk-local output slots): a caller that hands the rest of the arena to
 // something else (window_launch: the anchor pool) reserves them first and passes the block in
-size_t sketch_long_bytes(int n, const wm_sketch_job_t *h_jobs, bool allow_long, bool hpc)
+size_t sketch_long_bytes(int n, const wm_sketch_job_t *h_jobs, bool allow_long, bool hpc, bool even)
 {
 	int chunk = 0;
-	const int long_thr = sketch_long_thr(allow_long, &chunk, hpc);
+	const int long_thr = sketch_long_thr(allow_long, &chunk, hpc, even);
 	size_t bytes = 0;
-	if (hpc) {                                                  // the compacted sequences: a code and an end position per base at most
+	if (hpc || even) {                                          // the compacted sequences: a code and an end position per base at most; even k: an unambiguous code and a surviving step
 		uint64_t slots = 0;
 		for (int i = 0; i < n; ++i) if (h_jobs[i].len > 0) slots = std::max<uint64_t>(slots, h_jobs[i].scratch_off + (uint64_t)h_jobs[i].len);
-		return (size_t)(slots + 1) * 5 + 4096;
+		return (size_t)(slots + 1) * 5 * ((hpc ? 1 : 0) + (even ? 1 : 0)) + 4096;
 	}
 	if (long_thr > 0)
 		for (int i = 0; i < n; ++i)
@@ -755,8 +756,8 @@ int sketch_launch(wm_ctx_t *c, int n, const wm_sketch_job_t *h_jobs, const wm_sk
                          double *d_so, uint64_t *d_sx, uint32_t *d_sy, uint32_t *d_sl, wm128_t *d_out, int *d_cnt, bool allow_long, uint8_t *mem, size_t mem_bytes)
 {
 	int chunk = 0;
-	const bool hpc = c->skp.hpc != 0;
-	const int long_thr = sketch_long_thr(allow_long, &chunk, hpc);
+	const bool hpc = c->skp.hpc != 0, even = !(c->skp.k & 1);
+	const int long_thr = sketch_long_thr(allow_long, &chunk, hpc, even);
 	size_t mem_used = 0;
 	auto take = [&](size_t bytes) -> void* {                   // from the caller's block if there is one, else from the arena
 		if (!mem) return arena_take(c, bytes);
@@ -770,15 +771,21 @@ int sketch_launch(wm_ctx_t *c, int n, const wm_sketch_job_t *h_jobs, const wm_sk
 	if (long_thr > 0)
 		for (int i = 0; i < n; ++i)
 			if (h_jobs[i].len >= long_thr) { const int k = (h_jobs[i].len + chunk - 1) / chunk; lj.push_back(i); lj.push_back((int)n_ch); lj.push_back(k); n_ch += (size_t)k; }
-	uint8_t *d_hc = 0; uint32_t *d_he = 0;
-	if (hpc) {
+	uint8_t *d_hc = 0, *d_nn = 0; uint32_t *d_he = 0, *d_ei = 0;
+	if (hpc || even) {
 		uint64_t slots = 0;
 		for (int i = 0; i < n; ++i) if (h_jobs[i].len > 0) slots = std::max<uint64_t>(slots, h_jobs[i].scratch_off + (uint64_t)h_jobs[i].len);
-		d_he = (uint32_t*)take((size_t)(slots + 1) * 4); d_hc = (uint8_t*)take((size_t)slots + 1);
-		if (!d_he || !d_hc) return set_err(WM_ENOMEM, "sketch batch does not fit the arena (homopolymer-compressed copies)");
+		if (hpc) {
+			d_he = (uint32_t*)take((size_t)(slots + 1) * 4); d_hc = (uint8_t*)take((size_t)slots + 1);
+			if (!d_he || !d_hc) return set_err(WM_ENOMEM, "sketch batch does not fit the arena (homopolymer-compressed copies)");
+		}
+		if (even) {
+			d_ei = (uint32_t*)take((size_t)(slots + 1) * 4); d_nn = (uint8_t*)take((size_t)slots + 1);
+			if (!d_ei || !d_nn) return set_err(WM_ENOMEM, "sketch batch does not fit the arena (surviving steps of an even k)");
+		}
 	}
 	hipLaunchKernelGGL(sketch_coop_kernel, dim3(n), dim3(64), 0, c->stream, c->skp, d_jobs, d_ord, d_seqs, c->d_reads, c->d_reads_nm, c->d_bloom, d_so, d_sx, d_sy, d_sl, d_out, d_cnt, long_thr,
-	                   d_hc, d_he);
+	                   d_hc, d_he, d_nn, d_ei);
 	if (lj.empty()) return WM_OK;
 	UBuf<wm_sk_chunk_t> ch(n_ch, c);
 	UBuf<int> plj(lj.size(), c);
@@ -829,11 +836,11 @@ try {
 		uint64_t tot = 0;
 		wm_sketch_job_t *d_jobs = (wm_sketch_job_t*)arena_take(c, jb.size() * sizeof(wm_sketch_job_t));
 		uint8_t *d_seqs = (uint8_t*)arena_take(c, seqs_bytes + 64);
-		// odd k (every preset): one wavefront per sequence walking the chain of window minima (sketch_coop); even k: the palindrome rule
-		// of src/sketch.c:166 makes the slot stream data dependent -> the one-lane-per-sequence automaton (sketch_wave). WM_SKETCH_LANE=1 forces the latter.
+		// one wavefront per sequence walking the chain of window minima (sketch_coop; even k: over the steps that survive the palindrome rule of
+		// src/sketch.c:166). WM_SKETCH_LANE=1 forces the one-lane-per-sequence automaton (sketch_wave; k = 1 always takes it), A/B.
 		static const bool force_lane = getenv("WM_SKETCH_LANE") != 0;
-		const bool coop = (c->skp.k & 1) && c->skp.k >= 2 && !force_lane;
-		if (c->skp.hpc && !coop) return set_err(WM_EINVAL, "homopolymer compression on the device needs an odd k (got %d)", c->skp.k);
+		const bool coop = c->skp.k >= 2 && !force_lane;
+		if (c->skp.hpc && !coop) return set_err(WM_EINVAL, "homopolymer compression on the device needs the one-wavefront-per-sequence sketch (k = %d%s)", c->skp.k, force_lane ? ", WM_SKETCH_LANE set" : "");
 		uint64_t slots = 0;
 		for (size_t t = 0; t < todo.size(); ++t) {
 			const int i = todo[t];

@@ -451,13 +451,25 @@ struct wm_mapper_s {
 	std::vector<std::string> cmdline;      // argv of the front end, for the @PG line of SAM files (wm_mapper_set_cmdline)
 };
 
-// what the mapper's device path cannot serve is refused when the mapper is made, not in the middle of a mapping call: an even k (the fused
-// window call sketches with sketch_coop, which relies on k-mer != reverse complement, src/sketch.c:189). An index built with homopolymer compression
-// (MM_I_HPC, -H) is served since round 5: sketch_coop compacts every sequence into its runs first (src/sketch.c:152-163), mm_adjust_minier's HPC branch
-// (src/align.c:352-361) runs on the host.
+// what the mapper's device path does not serve is refused when the mapper is made, not in the middle of a mapping call. An even k: the
+// fused window call sketches it (sketch_kernel.h: sketch_even_steps, the palindrome rule of src/sketch.c:166), but the mapper serves it only to a process
+// that has opted in — wm_set_even_k(1), or WM_EVEN_K=1 in the environment, which is read whenever a mapper is made. An index built with homopolymer
+// compression (MM_I_HPC, -H) is served since round 5: sketch_coop compacts every sequence into its runs first (src/sketch.c:152-163), mm_adjust_minier's
+// HPC branch (src/align.c:352-361) runs on the host.
+static std::atomic<int> g_even_k(-1);          // -1: the environment decides
+static bool even_k_on()
+{
+	const int v = g_even_k.load(std::memory_order_relaxed);
+	if (v >= 0) return v != 0;
+	const char *e = getenv("WM_EVEN_K");
+	return e && atoi(e) != 0;
+}
+extern "C" void wm_set_even_k(int on) { g_even_k = on < 0 ? -1 : on ? 1 : 0; }
+extern "C" int wm_even_k_enabled(void) { return even_k_on(); }
 static int mapper_index_ok(const wm_index_t *idx)
 {
-	if (!(idx->ix.k & 1)) return set_err(WM_EINVAL, "k = %d: the mapper's device path needs an odd k (every preset of the reference has one)", idx->ix.k);
+	if (!(idx->ix.k & 1) && !even_k_on())
+		return set_err(WM_EINVAL, "k = %d: the mapper's device path needs an odd k (every preset of the reference has one) unless even k is switched on: wm_set_even_k(1) or WM_EVEN_K=1", idx->ix.k);
 	return WM_OK;
 }
 extern "C" int wm_mapper_create(wm_ctx_t *c, const wm_index_t *idx, const char *preset, int64_t flag, wm_mapper_t **out)

@@ -382,7 +382,7 @@ int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t
 		ord[i] = i;
 	}
 	if (bad >= 0) return set_err(WM_EINVAL, "window job %d: sequence / anchors outside their buffers (or wm_reads_upload missing)", bad);
-	if (!(c->skp.k & 1) || c->skp.k < 2) return set_err(WM_EINVAL, "wm_window_batch needs an odd k (got %d)", c->skp.k);
+	if (c->skp.k < 2) return set_err(WM_EINVAL, "wm_window_batch needs k >= 2 (got %d)", c->skp.k);
 	std::sort(ord.begin(), ord.end(), [&](int x, int y) { return sj[x].len != sj[y].len ? sj[x].len > sj[y].len : x < y; });     // sketch: longest first
 	// device buffers
 	wm_win_job_t *d_jobs = (wm_win_job_t*)arena_take(c, (size_t)n * sizeof(wm_win_job_t));
@@ -413,7 +413,7 @@ int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t
 		return set_err(WM_ENOMEM, "window batch does not fit the arena");
 	int *d_counts = (int*)(d_ctr + 4);
 	D.d_ctr = d_ctr;
-	const size_t long_bytes = sketch_long_bytes(n, sj.data(), !slot_full, c->skp.hpc != 0);       // chunked sketch of long sequences: its tables come before the pool takes the rest
+	const size_t long_bytes = sketch_long_bytes(n, sj.data(), !slot_full, c->skp.hpc != 0, !(c->skp.k & 1));       // chunked sketch of long sequences: its tables come before the pool takes the rest
 	uint8_t *d_long = long_bytes ? (uint8_t*)arena_take(c, long_bytes) : 0;
 	if (long_bytes && !d_long) return set_err(WM_ENOMEM, "window batch does not fit the arena");
 	// the rest of the arena is the anchor pool: 72 B per anchor (anchors 16, f|p|v|t 16, z/u 8, b 16, w 16) + the two dense result pools (24)

@@ -274,6 +274,18 @@ def ksw_dual_enabled():
     return bool(lib().wm_ksw_dual_enabled())
 
 
+def set_even_k(on):
+    """wm_set_even_k: let mappers made from now on serve an index with an even k (off by default; on < 0: back to what WM_EVEN_K in the environment says)"""
+    lib().wm_set_even_k.argtypes = [C.c_int]
+    lib().wm_set_even_k.restype = None
+    lib().wm_set_even_k(int(on))
+
+
+def even_k_enabled():
+    lib().wm_even_k_enabled.restype = C.c_int
+    return bool(lib().wm_even_k_enabled())
+
+
 def sdust_stats(reset=False):
     """wm_sdust_stats: the -T filter's process-wide account since the last reset"""
     out = np.zeros(5, np.float64)
