@@ -188,17 +188,17 @@ int wm_index_build(const char *fasta, const char *kmer_file, int k, int w, int n
  * the minimizers, run-length encode, sort by home slot, linear probing as a prefix maximum (index_table_on_device) — with the host's builder as the
  * fall-back when the arena is too small for the sort. Bit-identical to wm_index_build (tests/test_aux_gpu.py).
  * Any k from 2 to 28; contigs are sketched in groups that fit the context's arena (~26 B per base; an even k adds 5 B per base: the steps that survive the
- * palindrome rule of src/sketch.c:166, and keeps every contig on one wavefront, as -H does — see below). stats (optional, 4 doubles):
+ * palindrome rule of src/sketch.c:166; long contigs are sketched chunk by chunk, under -H / at an even k behind wm_sketch_set_step_chunks — see below). stats (optional, 4 doubles):
  * seconds reading + packing, sketching on the device (incl. transfers), building the table; minimizers. */
 int wm_index_build_gpu(wm_ctx_t *ctx, const char *fasta, const char *kmer_file, int k, int w, int n_threads, wm_index_t **out, double *stats);
 /* Both with the index flags of mm_idxopt_t::flag (src/minimap.h:41-43). Known here: MM_I_HPC = 1, the CLI's -H — minimizers over the homopolymer-
  * compressed sequence (src/sketch.c:152-163: a run of one base is one step, a minimizer sits on the last base of its last run and carries the summed length
  * of its k runs as span); a mapper on such an index sketches its reads the same way (the device sketch compacts every sequence into its runs first; with an
  * even k the runs whose k-mer is its own reverse complement are then taken out, src/sketch.c:160-166) and anchors are moved to the start of their runs before alignment (mm_adjust_minier, src/align.c:352-361). An index loaded from a file carries
- * its flag in the header. With -H the device build keeps every contig on ONE wavefront (the chunked sketch cuts in base space, the runs would have to be cut in
- * run space): for references with contigs of tens of Mb the host build (parallel per contig) is the faster of the two. The same holds for an even k, with or
- * without -H: a k-mer that equals its reverse complement skips the whole step of the winnowing automaton (src/sketch.c:166), the ring then runs over the
- * surviving steps, and sequences of WM_SKETCH_LONG codes and more stay on one wavefront — cutting chunks in step space is not done. */
+ * its flag in the header. With wm_sketch_set_step_chunks(1) long contigs are sketched chunk by chunk under -H and at an even k as they are at an odd k: the chunks are cut in base space, each
+ * wavefront first counts and then writes its part of the runs (-H) and of the steps that survive the palindrome rule (even k: a k-mer that equals its
+ * reverse complement skips the whole step of the winnowing automaton, src/sketch.c:166), and the two phases of the sketch then run over every chunk's range of
+ * such steps — see wm_sketch_set_step_chunks. */
 int wm_index_build_flag(const char *fasta, const char *kmer_file, int k, int w, int idx_flag, int n_threads, wm_index_t **out);
 int wm_index_build_gpu_flag(wm_ctx_t *ctx, const char *fasta, const char *kmer_file, int k, int w, int idx_flag, int n_threads, wm_index_t **out, double *stats);
 void wm_index_destroy(wm_index_t *idx);
@@ -316,6 +316,14 @@ int wm_sdust_batch(wm_ctx_t *ctx, int n, const uint8_t *seqs, size_t seqs_bytes,
 void wm_sdust_stats(double *out5, int reset);
 /* kernel time of the last sketch/seed/chain/window batch call (HIP events on the context stream), ms */
 float wm_last_aux_ms(const wm_ctx_t *ctx);
+/* Sequences of WM_SKETCH_LONG (65 536) codes and more are sketched in chunks of WM_SKETCH_CHUNK (16 384) positions, one wavefront per chunk, by
+ * wm_sketch_batch, the window calls and the device index build. wm_last_sketch_chunks: how many chunks the last such call on this context ran as wavefronts of
+ * their own (an index build: over all its contigs); 0 when everything ran one wavefront per sequence. Under -H and at an even k the chunks are cut in base
+ * space and sketched in step space; on = 0 keeps those two modes on one wavefront per sequence instead (A/B; results never depend on it), on = 1 chunks them,
+ * on < 0: back to the environment's WM_SKETCH_STEP_CHUNKS (read at every call while unset). Default 0: the two forms have not been timed against each
+ * other on a device yet, so for -H / even-k references with contigs of tens of Mb the host build (parallel per contig) may still be the faster one. */
+void wm_sketch_set_step_chunks(int on);
+int wm_last_sketch_chunks(const wm_ctx_t *ctx);
 
 /* ---- the mapper: replacement of kt_for(worker_for) (src/map.c:1164) ---------------------------------- */
 /* PROCESS-WIDE SETTINGS the library makes for the mapper (both are defaults: a value the caller has set wins; WM_NO_PROCESS_DEFAULTS=1 switches both off):

@@ -176,6 +176,19 @@ def build_emu_evenk():
     return out
 
 
+def build_emu_sketchsteps():
+    """tests/simt_emu/libwm_emu_sketchsteps.so: the chunked sketch of long sequences under -H and at an even k (csrc/sketch_kernel.h: sketch_steps_stage,
+    sketch_steps_scan, the two phases over slot space) on the emulator, one wavefront per chunk (tests/simt_emu/emu_sketchsteps.cpp)."""
+    emu = os.path.join(ROOT, "tests", "simt_emu")
+    out = os.path.join(emu, "libwm_emu_sketchsteps.so")
+    srcs = [os.path.join(emu, f) for f in ("emu_sketchsteps.cpp", "simt.h")] + [os.path.join(CSRC, f) for f in ("sketch_kernel.h", "reads2bit.h", "wm_internal.h")]
+    with _Lock(out):
+        if _newer(out, srcs):
+            _run_to(out, lambda o: ["g++", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
+                                    "-I" + emu, "-I" + CSRC, "-o", o, os.path.join(emu, "emu_sketchsteps.cpp")])
+    return out
+
+
 def build_emu_stripe(defines=()):
     """tests/simt_emu/libwm_emu_stripe[_<defines>].so: the stripe-pipelined ksw kernel alone on the emulator, with its event counters and the
     polling watchdog (tests/simt_emu/emu_stripe.cpp). ("WM_STRIPE_TEST_SLACK=...",) builds the variant whose bookkeeping margin is useless, so that
@@ -228,6 +241,7 @@ if __name__ == "__main__":
     build_emu_heapseed()
     build_emu_sdust()
     build_emu_evenk()
+    build_emu_sketchsteps()
     build_emu_stripe()
     build_emu_chain()
     build_harness()

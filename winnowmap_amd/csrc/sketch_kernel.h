@@ -1,5 +1,6 @@
-// sketch_kernel.h — weighted robust-winnowing minimizers (mm_sketch, src/sketch.c:128-219) on gfx950. Homopolymer compression (:152-163) in the
-// one-wavefront-per-sequence kernel only (sketch_coop: sketch_hpc_steps compacts the sequence into its runs, the two phases then run over the runs).
+// sketch_kernel.h — weighted robust-winnowing minimizers (mm_sketch, src/sketch.c:128-219) on gfx950. Homopolymer compression (:152-163) and an even k (:166)
+// compact the sequence into the automaton's steps first — one wavefront per sequence (sketch_coop: sketch_hpc_steps, sketch_even_steps) or, for a long
+// sequence, one wavefront per chunk (sketch_steps_*: count, scan, scatter) — and the two phases then run over the steps.
 //
 // Mapping: ONE LANE per (sub)sequence — stage 1 of Winnowmap2 sketches ~9 windows per read, so a mini-batch holds
 // 10^4..10^6 independent sequences and the machine fills with thread-level parallelism; the winnowing automaton
@@ -223,7 +224,9 @@ WM_DEV void sketch_p1_range_t(const wm_sketch_params_t P, long long soff, int n,
 			V<int> hit = -1;
 			WM_IF(i < begin)
 				vbool amb = false;
-				if constexpr (PACKED) amb = rd2_is_n(nm, cast<long long>(i) + soff); else amb = cast<int>(gld(seqs, cast<long long>(i) + soff)) >= 4;
+				V<int> a = i;                            // (EVEN: the step that survived into the slot, as below)
+				if constexpr (EVEN) a = cast<int>(gld(ei, i));
+				if constexpr (PACKED) amb = rd2_is_n(nm, cast<long long>(a) + soff); else amb = cast<int>(gld(seqs, cast<long long>(a) + soff)) >= 4;
 				WM_IF(amb) hit = i; WM_END
 			WM_END
 			const int mx = readlane(wave_scan_max(hit), 63);
@@ -395,13 +398,15 @@ WM_DEV int sketch_p2_range(const wm_sketch_params_t P, int n, const double *so, 
 
 // homopolymer compression (src/sketch.c:152-163) as a compaction: the STEPS of the reference's automaton in order — every run of one unambiguous base, every
 // ambiguous base on its own (:175) — hc[s] = the step's code, he[s] = the position of its last base (where :159 leaves i). Returns the number of steps.
-WM_DEV int sketch_hpc_steps(long long soff, int n, const uint8_t *seqs, const uint64_t *pk, const uint64_t *nm, uint8_t *hc, uint32_t *he)
+// [b, e): the bases looked at, `at`: the first slot written — a chunk of a long sequence (sketch_steps_stage) or (0, n, 0) the whole of it; hc == 0: the steps are
+// counted only. *codes (optional): how many of them are unambiguous.
+WM_DEV int sketch_runs_range(long long soff, int n, const uint8_t *seqs, const uint64_t *pk, const uint64_t *nm, int b, int e, int at, uint8_t *hc, uint32_t *he, int *codes = 0)
 {
 	const V<int> ln = lane();
-	int S = 0;
-	for (int t0 = 0; t0 < n; t0 += 64) {
+	int S = 0, C = 0;
+	for (int t0 = b; t0 < e; t0 += 64) {
 		const V<int> i = ln + t0;
-		const vbool in = i < n;
+		const vbool in = i < e;
 		V<int> c = 4, cn = 5;
 		WM_IF(in)
 			c = sk_code(seqs, pk, nm, V<long long>(soff), cast<long long>(i));
@@ -409,11 +414,19 @@ WM_DEV int sketch_hpc_steps(long long soff, int n, const uint8_t *seqs, const ui
 		WM_END
 		const vbool last = in && (c >= 4 || cn != c);
 		const uint64_t bm = ballot(last);
-		const V<int> at = mbcnt(bm) + S;
-		WM_IF(last) gst(hc, at, cast<uint8_t>(c)); gst(he, at, cast<uint32_t>(i)); WM_END
+		if (hc) {
+			const V<int> to = mbcnt(bm) + (at + S);
+			WM_IF(last) gst(hc, to, cast<uint8_t>(c)); gst(he, to, cast<uint32_t>(i)); WM_END
+		}
 		S += popc64(bm);
+		C += popc64(ballot(last && c < 4));
 	}
+	if (codes) *codes = C;
 	return S;
+}
+WM_DEV int sketch_hpc_steps(long long soff, int n, const uint8_t *seqs, const uint64_t *pk, const uint64_t *nm, uint8_t *hc, uint32_t *he)
+{
+	return sketch_runs_range(soff, n, seqs, pk, nm, 0, n, 0, hc, he);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -477,6 +490,114 @@ WM_DEV int sketch_even_steps(int k, long long soff, int n, const uint8_t *seqs, 
 	return U;
 }
 
+// phase 1 over slots [begin, end) of a sequence that was compacted into n steps (P.hpc or an even k; P.hpc: its runs hc / he; even k: the surviving steps ei, of the runs under P.hpc)
+WM_DEV void sketch_p1_steps(const wm_sketch_params_t P, long long soff, int n, const uint8_t *seqs, const uint64_t *pk, const uint64_t *nm, const uint8_t *bloom_bits,
+                            double *so, uint64_t *sx, uint32_t *sy, uint32_t *sl, int begin, int end, const uint8_t *hc, const uint32_t *he, const uint32_t *ei)
+{
+	const bool even = !(P.k & 1);
+	if (P.hpc) {
+		if (even) sketch_p1_range_t<false, true, true>(P, 0, n, hc, pk, nm, bloom_bits, so, sx, sy, sl, begin, end, he, ei);
+		else sketch_p1_range_t<false, true>(P, 0, n, hc, pk, nm, bloom_bits, so, sx, sy, sl, begin, end, he);
+	} else if (soff & (long long)WM_RD_PACKED_BIT) sketch_p1_range_t<true, false, true>(P, soff & (long long)(WM_RD_PACKED_BIT - 1), n, seqs, pk, nm, bloom_bits, so, sx, sy, sl, begin, end, 0, ei);
+	else sketch_p1_range_t<false, false, true>(P, soff, n, seqs, pk, nm, bloom_bits, so, sx, sy, sl, begin, end, 0, ei);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Step space on several wavefronts: a long sequence under P.hpc / at an even k. sketch_hpc_steps and sketch_even_steps are stream compactions, positional
+// once the ranks are known, so each of them becomes count per chunk -> exclusive scan over the sequence's chunks -> scatter, one wavefront per chunk of BASES
+// (the host's chunk table) and a kernel boundary between the three:
+//   SK_RUNS  (P.hpc)  the step ends among the chunk's bases -> hc / he. A chunk inside one long run holds none; a run may span many chunks.
+//   SK_CODES (even k) the unambiguous codes among the chunk's steps — its bases, or its runs under P.hpc — -> nn
+//   SK_SURV  (even k) the steps that survive the palindrome rule -> ei. Step a of rank r reads nn[r - k + 1 .. r], which a chunk before may have written:
+//                     nn is complete (a kernel boundary) before any chunk tests. A chunk inside an (AT)n array has no survivor.
+// After the last stage every chunk's range of SLOTS (runs, survivors, survivors of runs) replaces its range of bases in the chunk table, and phase 1, the sync
+// search, phase 2 and the gather run over slot space as they do over base space at an odd k: ranges are unequal, some are empty (such a chunk has no sync
+// position and is absorbed), and the sequence's n is its total number of slots.
+// T: per chunk and stage how many items the chunk holds and the first slot it writes; tot[3 q + stage]: the total of long sequence q.
+// ------------------------------------------------------------------------------------------------------------------------------
+enum { SK_RUNS = 0, SK_CODES = 1, SK_SURV = 2 };
+struct wm_sk_steps_t { int *cnt[3], *off[3], *tot; };
+
+// the unambiguous codes among steps [b, e) (as sk_code reads them) to nn[at ..], in order; nn == 0: counted only. Returns their number.
+WM_DEV int sketch_codes_range(long long soff, const uint8_t *seqs, const uint64_t *pk, const uint64_t *nm, int b, int e, int at, uint8_t *nn)
+{
+	const V<int> ln = lane();
+	int R = 0;
+	for (int t0 = b; t0 < e; t0 += 64) {
+		const V<int> i = ln + t0;
+		V<int> c = 4;
+		WM_IF(i < e) c = sk_code(seqs, pk, nm, V<long long>(soff), cast<long long>(i)); WM_END
+		const vbool base = c < 4;
+		const uint64_t bm = ballot(base);
+		if (nn) { WM_IF(base) gst(nn, mbcnt(bm) + (at + R), cast<uint8_t>(c)); WM_END }
+		R += popc64(bm);
+	}
+	return R;
+}
+
+// the steps of [b, e) that survive the palindrome rule (sketch_even_steps, pass 2) to ei[at ..]; ei == 0: counted only. r0: unambiguous codes before step b;
+// nn: complete up to the last code of step e - 1. Returns their number.
+WM_DEV int sketch_surv_range(int k, long long soff, const uint8_t *seqs, const uint64_t *pk, const uint64_t *nm, int b, int e, int r0, const uint8_t *nn, int at, uint32_t *ei)
+{
+	const V<int> ln = lane();
+	int U = 0, R = r0;
+	for (int t0 = b; t0 < e; t0 += 64) {
+		const V<int> i = ln + t0;
+		const vbool in = i < e;
+		V<int> c = 4;
+		WM_IF(in) c = sk_code(seqs, pk, nm, V<long long>(soff), cast<long long>(i)); WM_END
+		const vbool base = c < 4;
+		const uint64_t bm = ballot(base);
+		const V<int> r = mbcnt(bm) + R;
+		vbool pal = base && r >= k - 1;
+		for (int j = 0; j < k / 2 && any(pal); ++j) {
+			WM_IF(pal) pal = cast<int>(gld(nn, r - j)) + cast<int>(gld(nn, r - (k - 1) + j)) == 3; WM_END
+		}
+		const vbool keep = in && !pal;
+		const uint64_t km = ballot(keep);
+		if (ei) { WM_IF(keep) gst(ei, mbcnt(km) + (at + U), cast<uint32_t>(i)); WM_END }
+		U += popc64(km);
+		R += popc64(bm);
+	}
+	return U;
+}
+
+// one stage of chunk b (bases [cb, ce) of job jb; hc .. ei: the job's scratch): scatter == false counts into T.cnt[stage][b], true writes from T.off[stage][b] on
+// (SK_RUNS then also leaves the chunk's SK_CODES count: the unambiguous ones among its runs)
+WM_DEV void sketch_steps_stage(const wm_sketch_params_t P, const wm_sketch_job_t jb, const uint8_t *seqs, const uint64_t *pk, const uint64_t *nm, int b, int cb, int ce,
+                               const wm_sk_steps_t T, int stage, bool scatter, uint8_t *hc, uint32_t *he, uint8_t *nn, uint32_t *ei)
+{
+	int res = 0, into = stage;
+	const int at = scatter ? T.off[stage][b] : 0;
+	if (stage == SK_RUNS) {
+		const int S = sketch_runs_range((long long)jb.seq_off, jb.len, seqs, pk, nm, cb, ce, at, scatter ? hc : 0, he, &res);
+		if (scatter) into = SK_CODES; else res = S;
+	} else {
+		long long soff = (long long)jb.seq_off;          // the chunk's steps: its bases, or (P.hpc) its runs
+		if (P.hpc) { soff = 0; seqs = hc; cb = T.off[SK_RUNS][b]; ce = cb + T.cnt[SK_RUNS][b]; }
+		if (stage == SK_CODES) res = sketch_codes_range(soff, seqs, pk, nm, cb, ce, at, scatter ? nn : 0);
+		else res = sketch_surv_range(P.k, soff, seqs, pk, nm, cb, ce, T.off[SK_CODES][b], nn, at, scatter ? ei : 0);
+		if (scatter) return;
+	}
+	WM_IF(lane() == 0) gst(T.cnt[into], V<long long>((long long)b), V<int>(res)); WM_END
+}
+
+// exclusive scan of cnt[0 .. nc) into off[0 .. nc) on one wavefront; returns the total
+WM_DEV int sketch_steps_scan(const int *cnt, int *off, int nc)
+{
+	const V<int> ln = lane();
+	int tot = 0;
+	for (int t0 = 0; t0 < nc; t0 += 64) {
+		const V<int> i = ln + t0;
+		V<int> v = 0;
+		WM_IF(i < nc) v = gld(cnt, i); WM_END
+		const V<int> inc = wave_scan_add(v);
+		WM_IF(i < nc) gst(off, i, inc - v + tot); WM_END
+		tot += readlane(inc, 63);
+	}
+	return tot;
+}
+
 // even k: hc / he as in sketch_coop, nn / ei = scratch of jb.len entries each (sketch_even_steps)
 WM_DEV void sketch_coop_even(const wm_sketch_params_t P, const wm_sketch_job_t jb, const uint8_t *seqs, const uint64_t *pk, const uint64_t *nm, const uint8_t *bloom_bits,
                              double *so, uint64_t *sx, uint32_t *sy, uint32_t *sl, wm128_t *out, int *count_out, uint8_t *hc, uint32_t *he, uint8_t *nn, uint32_t *ei)
@@ -487,14 +608,9 @@ WM_DEV void sketch_coop_even(const wm_sketch_params_t P, const wm_sketch_job_t j
 		const int S = sketch_hpc_steps(soff, jb.len, seqs, pk, nm, hc, he);
 		mem_sync();
 		U = sketch_even_steps(P.k, 0, S, hc, pk, nm, nn, ei);
-		mem_sync();
-		sketch_p1_range_t<false, true, true>(P, 0, U, hc, pk, nm, bloom_bits, so, sx, sy, sl, 0, U, he, ei);
-	} else {
-		U = sketch_even_steps(P.k, soff, jb.len, seqs, pk, nm, nn, ei);
-		mem_sync();
-		if (soff & (long long)WM_RD_PACKED_BIT) sketch_p1_range_t<true, false, true>(P, soff & (long long)(WM_RD_PACKED_BIT - 1), U, seqs, pk, nm, bloom_bits, so, sx, sy, sl, 0, U, 0, ei);
-		else sketch_p1_range_t<false, false, true>(P, soff, U, seqs, pk, nm, bloom_bits, so, sx, sy, sl, 0, U, 0, ei);
-	}
+	} else U = sketch_even_steps(P.k, soff, jb.len, seqs, pk, nm, nn, ei);
+	mem_sync();
+	sketch_p1_steps(P, soff, U, seqs, pk, nm, bloom_bits, so, sx, sy, sl, 0, U, hc, he, ei);
 	mem_sync();
 	const int n_out = sketch_p2_range(P, U, so, sx, sy, sl, 0, false, -1, out + jb.out_off, jb.cap);
 	WM_IF(lane() == 0) gst(count_out, V<long long>(0), V<int>(n_out)); WM_END
@@ -508,7 +624,7 @@ WM_DEV void sketch_coop(const wm_sketch_params_t P, const wm_sketch_job_t jb, co
 	if (P.hpc) {
 		const int S = sketch_hpc_steps((long long)jb.seq_off, jb.len, seqs, pk, nm, hc, he);
 		mem_sync();
-		sketch_p1_range_t<false, true>(P, 0, S, hc, pk, nm, bloom_bits, so, sx, sy, sl, 0, S, he);
+		sketch_p1_steps(P, 0, S, seqs, pk, nm, bloom_bits, so, sx, sy, sl, 0, S, hc, he, 0);
 		mem_sync();
 		const int n_hpc = sketch_p2_range(P, S, so, sx, sy, sl, 0, false, -1, out + jb.out_off, jb.cap);
 		WM_IF(lane() == 0) gst(count_out, V<long long>(0), V<int>(n_hpc)); WM_END

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(64) void sketch_long_sync_kernel(wm_sketch_params_t
 	if (threadIdx.x == 0) sync[blockIdx.x] = t;
 }
 __global__ __launch_bounds__(64) void sketch_long_p2_kernel(wm_sketch_params_t P, const wm_sketch_job_t *jobs, const wm_sk_chunk_t *chunks, int n_chunks, const double *so, const uint64_t *sx,
-                                                             const uint32_t *sy, const uint32_t *sl, const int *sync, wm128_t *cout, int *ccount)
+                                                             const uint32_t *sy, const uint32_t *sl, const int *sync, wm128_t *cout, int *ccount, const int *n_slots)
 {
 	WM_SETPRIO(2);
 	const int b = blockIdx.x;
@@ -63,9 +63,40 @@ __global__ __launch_bounds__(64) void sketch_long_p2_kernel(wm_sketch_params_t P
 		int t_stop = -1;
 		for (int d = b + 1; d < n_chunks && chunks[d].job == ch.job && t_stop < 0; ++d) t_stop = sync[d];
 		const wm_sketch_job_t jb = jobs[ch.job];
-		n = wmk::sketch_p2_range(P, jb.len, so + jb.scratch_off, sx + jb.scratch_off, sy + jb.scratch_off, sl + jb.scratch_off, ch.first ? 0 : sync[b], !ch.first, t_stop, cout + ch.out_off, ch.cap);
+		n = wmk::sketch_p2_range(P, n_slots ? n_slots[3 * ch.pad] : jb.len, so + jb.scratch_off, sx + jb.scratch_off, sy + jb.scratch_off, sl + jb.scratch_off, ch.first ? 0 : sync[b], !ch.first, t_stop, cout + ch.out_off, ch.cap);
 	}
 	if (threadIdx.x == 0) ccount[b] = n;
+}
+// ---- the same under homopolymer compression / at an even k (sketch_kernel.h: "step space on several wavefronts"): the chunks are cut in base space as above, the
+// stages below compact every long job into its steps — per stage: count per chunk | scan per job | scatter per chunk —, sketch_steps_fix_kernel turns every
+// chunk's range of bases into its range of slots, and phase 1 / sync / phase 2 / gather run over the slots (chunk.pad = the job's index among the long jobs)
+__global__ __launch_bounds__(64) void sketch_steps_stage_kernel(wm_sketch_params_t P, const wm_sketch_job_t *jobs, const wm_sk_chunk_t *chunks, const uint8_t *seqs, const uint64_t *rpk,
+                                                                 const uint64_t *rnm, wmk::wm_sk_steps_t T, int stage, int scatter, uint8_t *hc, uint32_t *he, uint8_t *nn, uint32_t *ei)
+{
+	const wm_sk_chunk_t ch = chunks[blockIdx.x];
+	const wm_sketch_job_t jb = jobs[ch.job];
+	wmk::sketch_steps_stage(P, jb, seqs, rpk, rnm, (int)blockIdx.x, ch.begin, ch.end, T, stage, scatter != 0, hc ? hc + jb.scratch_off : 0, he ? he + jb.scratch_off : 0,
+	                        nn ? nn + jb.scratch_off : 0, ei ? ei + jb.scratch_off : 0);
+}
+__global__ __launch_bounds__(64) void sketch_steps_scan_kernel(const int *long_jobs, wmk::wm_sk_steps_t T, int stage)
+{
+	const int c0 = long_jobs[3 * blockIdx.x + 1], nc = long_jobs[3 * blockIdx.x + 2];
+	const int tot = wmk::sketch_steps_scan(T.cnt[stage] + c0, T.off[stage] + c0, nc);
+	if (threadIdx.x == 0) T.tot[3 * blockIdx.x + stage] = tot;
+}
+__global__ __launch_bounds__(64) void sketch_steps_fix_kernel(wm_sk_chunk_t *chunks, int n_chunks, wmk::wm_sk_steps_t T, int stage)
+{
+	const int b = blockIdx.x * 64 + threadIdx.x;
+	if (b < n_chunks) { chunks[b].begin = T.off[stage][b]; chunks[b].end = T.off[stage][b] + T.cnt[stage][b]; }
+}
+__global__ __launch_bounds__(64) void sketch_steps_p1_kernel(wm_sketch_params_t P, const wm_sketch_job_t *jobs, const wm_sk_chunk_t *chunks, const uint8_t *seqs, const uint64_t *rpk,
+                                                              const uint64_t *rnm, const uint8_t *bloom, double *so, uint64_t *sx, uint32_t *sy, uint32_t *sl, const int *n_slots,
+                                                              const uint8_t *hc, const uint32_t *he, const uint32_t *ei)
+{
+	const wm_sk_chunk_t ch = chunks[blockIdx.x];
+	const wm_sketch_job_t jb = jobs[ch.job];
+	wmk::sketch_p1_steps(P, (long long)jb.seq_off, n_slots[3 * ch.pad], seqs, rpk, rnm, bloom, so + jb.scratch_off, sx + jb.scratch_off, sy + jb.scratch_off, sl + jb.scratch_off, ch.begin, ch.end,
+	                     hc ? hc + jb.scratch_off : 0, he ? he + jb.scratch_off : 0, ei ? ei + jb.scratch_off : 0);
 }
 // long_jobs[3 i ..]: job, its first chunk, its chunk count
 __global__ __launch_bounds__(64) void sketch_long_gather_kernel(const wm_sketch_job_t *jobs, const int *long_jobs, const wm_sk_chunk_t *chunks, const wm128_t *cout, const int *ccount,
@@ -656,11 +687,11 @@ int wm_index_build_seqs_dev(wm_ctx_t *c, const wm::IdxOpt &io, std::vector<std::
 	c->d_bloom = d_bloom;
 	c->skp.w = w; c->skp.k = k; c->skp.table_bits = (uint32_t)ix.bloom.table_bits; c->skp.salt0 = ix.bloom.salt[0]; c->skp.salt1 = ix.bloom.salt[1]; c->skp.hpc = io.flag & 1;
 	std::vector<wm::m128> all;
-	int rc = WM_OK;
+	int rc = WM_OK, n_chunks = 0;
 	const size_t budget = (size_t)(c->arena_bytes * 0.85);
 	for (size_t g0 = 0; g0 < seqs.size() && rc == WM_OK;) {             // groups of contigs that fit the arena: 1 B codes + 24 B scratch + 2 B output + 4 B chunk-local output (+ tables) per base
 		size_t g1 = g0, bases = 0;
-		const size_t per_base = 34 + ((io.flag & 1) ? 5 : 0) + (!(k & 1) ? 5 : 0);   // (+ the homopolymer-compressed copy: a code and an end position per base; + even k: an unambiguous code and a surviving step per base)
+		const size_t per_base = 34 + ((io.flag & 1) ? 5 : 0) + (!(k & 1) ? 5 : 0);   // (+ the homopolymer-compressed copy: a code and an end position per base; + even k: an unambiguous code and a surviving step per base; their count / offset tables, 24 B per chunk, sit in the slack of the 34)
 		while (g1 < seqs.size() && (g1 == g0 || (bases + seqs[g1].size()) * per_base + 4096 * (g1 - g0 + 1) <= budget)) { bases += seqs[g1].size(); ++g1; }
 		if (bases * per_base > budget) { rc = set_err(WM_ENOMEM, "contig %zu (%zu bases) needs %.1f GB of arena for the device sketch", g0, seqs[g0].size(), seqs[g0].size() * per_base / 1073741824.0); break; }
 		const int n = (int)(g1 - g0);
@@ -674,6 +705,7 @@ int wm_index_build_seqs_dev(wm_ctx_t *c, const wm::IdxOpt &io, std::vector<std::
 		rc = sketch_batch_impl(c, n, codes.get(), tot, off.data(), len.data(), 0, mv.data(), mv.size(), ooff.data(), cnt.data());
 		if (rc == WM_ENOMEM && strstr(wm_err_text(), "minimizer output pool")) { mv.resize(bases + n + 1); rc = sketch_batch_impl(c, n, codes.get(), tot, off.data(), len.data(), 0, mv.data(), mv.size(), ooff.data(), cnt.data()); }
 		if (rc) break;
+		n_chunks += c->sketch_chunks;
 		for (int i = 0; i < n; ++i)
 			for (int t = 0; t < cnt[i]; ++t) { wm::m128 e; e.x = mv[ooff[i] + t].x; e.y = mv[ooff[i] + t].y | (uint64_t)(g0 + i) << 32; all.push_back(e); }     // rid (src/sketch.c:172)
 		g0 = g1;
@@ -690,6 +722,7 @@ int wm_index_build_seqs_dev(wm_ctx_t *c, const wm::IdxOpt &io, std::vector<std::
 	if (trc < 0) { delete h; return trc; }
 	if (trc > 0) { t_tab_dev = -1; wm::index_table_from_minimizers(ix, all); }
 	if (stats) { stats[0] = (t1 - t0) * 1e-3; stats[1] = (t2 - t1) * 1e-3; stats[2] = (now_ms() - t2) * 1e-3; stats[3] = n_mini; }
+	c->sketch_chunks = n_chunks;                   // (wm_last_sketch_chunks: over all groups of contigs)
 	c->aux_ms = (float)(t_tab_dev * 1e3);          // (wm_last_aux_ms: the device table build of this call, < 0 = built on the host)
 	*out = h;
 	return WM_OK;
@@ -724,16 +757,28 @@ extern "C" int wm_sketch_batch(wm_ctx_t *c, int n, const uint8_t *seqs, size_t s
 // The one-wavefront-per-sequence sketch of `n` jobs (h_jobs = the host copy of d_jobs) and, for sequences of WM_SKETCH_LONG (65 536) codes and more, the
 // chunked form: WM_SKETCH_CHUNK (16 384) positions per wavefront. allow_long = false (a repeat with full-size slots): everything on one wavefront each.
 // Everything is queued on the context's stream; with long jobs the call waits once (its chunk tables are staged in the pinned slab).
+// Homopolymer compression and an even k take the chunked form too, in step space (sketch_steps_* kernels), when wm_sketch_set_step_chunks(1) /
+// WM_SKETCH_STEP_CHUNKS=1 asks for it; otherwise they stay on one wavefront per sequence.
+static std::atomic<int> g_step_chunks(-1);     // -1: the environment decides
+static bool step_chunks_on()
+{
+	const int v = g_step_chunks.load(std::memory_order_relaxed);
+	if (v >= 0) return v != 0;
+	const char *e = getenv("WM_SKETCH_STEP_CHUNKS");
+	return e ? atoi(e) != 0 : false;          // (off until an A/B on the device has shown it the faster form: DESIGN.md "Even k")
+}
+extern "C" void wm_sketch_set_step_chunks(int on) { g_step_chunks = on < 0 ? -1 : on ? 1 : 0; }
+extern "C" int wm_last_sketch_chunks(const wm_ctx_t *c) { return c ? c->sketch_chunks : 0; }
 static int sketch_long_thr(bool allow_long, int *chunk_out, bool hpc = false, bool even = false)
 {
-	if (hpc || even) { *chunk_out = 16384; return 0; }         // homopolymer compression, even k: every sequence on one wavefront (the chunks would have to be cut in run / step space)
 	static const int long_env = getenv("WM_SKETCH_LONG") ? atoi(getenv("WM_SKETCH_LONG")) : 65536;
 	static const int chunk = std::max(1024, getenv("WM_SKETCH_CHUNK") ? atoi(getenv("WM_SKETCH_CHUNK")) : 16384);
 	*chunk_out = chunk;
+	if ((hpc || even) && !step_chunks_on()) return 0;
 	return allow_long && long_env > 0 ? std::max(long_env, 2 * chunk) : 0;
 }
-// device bytes sketch_launch needs on top of the caller's buffers (chunk tables + chunk-local output slots): a caller that hands the rest of the arena to
-// something else (window_launch: the anchor pool) reserves them first and passes the block in
+// device bytes sketch_launch needs on top of the caller's buffers (chunk tables + chunk-local output slots; the compacted copies of hpc / even): a caller that
+// hands the rest of the arena to something else (window_launch: the anchor pool) reserves them first and passes the block in
 size_t sketch_long_bytes(int n, const wm_sketch_job_t *h_jobs, bool allow_long, bool hpc, bool even)
 {
 	int chunk = 0;
@@ -742,13 +787,14 @@ size_t sketch_long_bytes(int n, const wm_sketch_job_t *h_jobs, bool allow_long, 
 	if (hpc || even) {                                          // the compacted sequences: a code and an end position per base at most; even k: an unambiguous code and a surviving step
 		uint64_t slots = 0;
 		for (int i = 0; i < n; ++i) if (h_jobs[i].len > 0) slots = std::max<uint64_t>(slots, h_jobs[i].scratch_off + (uint64_t)h_jobs[i].len);
-		return (size_t)(slots + 1) * 5 * ((hpc ? 1 : 0) + (even ? 1 : 0)) + 4096;
+		bytes = (size_t)(slots + 1) * 5 * ((hpc ? 1 : 0) + (even ? 1 : 0)) + 4096;
 	}
 	if (long_thr > 0)
 		for (int i = 0; i < n; ++i)
 			if (h_jobs[i].len >= long_thr) {
 				const size_t k = ((size_t)h_jobs[i].len + chunk - 1) / chunk;
 				bytes += k * (sizeof(wm_sk_chunk_t) + 8 + ((size_t)chunk / 4 + 64 + 1) * sizeof(wm128_t)) + 12 + 1024;
+				if (hpc || even) bytes += k * 24 + 12;              // (per chunk and stage a count and an offset, per job the three totals)
 			}
 	return bytes ? bytes + 4096 : 0;
 }
@@ -786,6 +832,7 @@ int sketch_launch(wm_ctx_t *c, int n, const wm_sketch_job_t *h_jobs, const wm_sk
 	}
 	hipLaunchKernelGGL(sketch_coop_kernel, dim3(n), dim3(64), 0, c->stream, c->skp, d_jobs, d_ord, d_seqs, c->d_reads, c->d_reads_nm, c->d_bloom, d_so, d_sx, d_sy, d_sl, d_out, d_cnt, long_thr,
 	                   d_hc, d_he, d_nn, d_ei);
+	if (allow_long) c->sketch_chunks = (int)n_ch;              // (wm_last_sketch_chunks; a repeat with full-size slots belongs to the call that asked for it)
 	if (lj.empty()) return WM_OK;
 	UBuf<wm_sk_chunk_t> ch(n_ch, c);
 	UBuf<int> plj(lj.size(), c);
@@ -795,7 +842,7 @@ int sketch_launch(wm_ctx_t *c, int n, const wm_sketch_job_t *h_jobs, const wm_sk
 		const int i = lj[q], c0 = lj[q + 1], k = lj[q + 2];
 		for (int t = 0; t < k; ++t) {
 			wm_sk_chunk_t &x = ch[(size_t)c0 + t];
-			x.job = i; x.begin = t * chunk; x.end = std::min(h_jobs[i].len, (t + 1) * chunk); x.first = t == 0; x.pad = 0;
+			x.job = i; x.begin = t * chunk; x.end = std::min(h_jobs[i].len, (t + 1) * chunk); x.first = t == 0; x.pad = hpc || even ? (int)(q / 3) : 0;
 			x.cap = (x.end - x.begin) / 4 + 64;                   // (a chunk's wavefront also covers the chunks it absorbs: twice the job slot's density; beyond that the job is repeated)
 			x.out_off = co; co += (uint64_t)x.cap;
 		}
@@ -806,9 +853,33 @@ int sketch_launch(wm_ctx_t *c, int n, const wm_sketch_job_t *h_jobs, const wm_sk
 	if (!d_ch || !d_lj || !d_sync || !d_cc || !d_cout) return set_err(WM_ENOMEM, "sketch batch does not fit the arena");
 	HIPCHK(hipMemcpyAsync(d_ch, ch.data(), n_ch * sizeof(wm_sk_chunk_t), hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipMemcpyAsync(d_lj, plj.data(), lj.size() * 4, hipMemcpyHostToDevice, c->stream));
-	hipLaunchKernelGGL(sketch_long_p1_kernel, dim3((unsigned)n_ch), dim3(64), 0, c->stream, c->skp, d_jobs, d_ch, d_seqs, c->d_reads, c->d_reads_nm, c->d_bloom, d_so, d_sx, d_sy, d_sl);
+	const int *d_nslot = 0;
+	if (hpc || even) {                                          // step space: the long jobs' runs / surviving steps first, the chunk table then holds slot ranges
+		const unsigned nl = (unsigned)(lj.size() / 3);
+		int *d_tab = (int*)take((6 * n_ch + 3 * (size_t)nl) * 4 + 64);
+		if (!d_tab) return set_err(WM_ENOMEM, "sketch batch does not fit the arena");
+		wmk::wm_sk_steps_t T;
+		for (int g = 0; g < 3; ++g) { T.cnt[g] = d_tab + (size_t)g * n_ch; T.off[g] = d_tab + (size_t)(3 + g) * n_ch; }
+		T.tot = d_tab + 6 * n_ch;
+		auto stage = [&](int g, int scatter) {
+			hipLaunchKernelGGL(sketch_steps_stage_kernel, dim3((unsigned)n_ch), dim3(64), 0, c->stream, c->skp, d_jobs, d_ch, d_seqs, c->d_reads, c->d_reads_nm, T, g, scatter, d_hc, d_he, d_nn, d_ei);
+		};
+		auto scan = [&](int g) { hipLaunchKernelGGL(sketch_steps_scan_kernel, dim3(nl), dim3(64), 0, c->stream, d_lj, T, g); };
+		if (hpc) { stage(wmk::SK_RUNS, 0); scan(wmk::SK_RUNS); stage(wmk::SK_RUNS, 1); }      // (the scatter of the runs leaves their SK_CODES counts)
+		if (even) {
+			if (!hpc) stage(wmk::SK_CODES, 0);
+			scan(wmk::SK_CODES); stage(wmk::SK_CODES, 1);
+			stage(wmk::SK_SURV, 0); scan(wmk::SK_SURV); stage(wmk::SK_SURV, 1);
+		}
+		const int last = even ? wmk::SK_SURV : wmk::SK_RUNS;
+		hipLaunchKernelGGL(sketch_steps_fix_kernel, dim3((unsigned)((n_ch + 63) / 64)), dim3(64), 0, c->stream, d_ch, (int)n_ch, T, last);
+		d_nslot = T.tot + last;
+		hipLaunchKernelGGL(sketch_steps_p1_kernel, dim3((unsigned)n_ch), dim3(64), 0, c->stream, c->skp, d_jobs, d_ch, d_seqs, c->d_reads, c->d_reads_nm, c->d_bloom, d_so, d_sx, d_sy, d_sl, d_nslot,
+		                   d_hc, d_he, d_ei);
+	} else
+		hipLaunchKernelGGL(sketch_long_p1_kernel, dim3((unsigned)n_ch), dim3(64), 0, c->stream, c->skp, d_jobs, d_ch, d_seqs, c->d_reads, c->d_reads_nm, c->d_bloom, d_so, d_sx, d_sy, d_sl);
 	hipLaunchKernelGGL(sketch_long_sync_kernel, dim3((unsigned)n_ch), dim3(64), 0, c->stream, c->skp, d_jobs, d_ch, d_so, d_sync);
-	hipLaunchKernelGGL(sketch_long_p2_kernel, dim3((unsigned)n_ch), dim3(64), 0, c->stream, c->skp, d_jobs, d_ch, (int)n_ch, d_so, d_sx, d_sy, d_sl, d_sync, d_cout, d_cc);
+	hipLaunchKernelGGL(sketch_long_p2_kernel, dim3((unsigned)n_ch), dim3(64), 0, c->stream, c->skp, d_jobs, d_ch, (int)n_ch, d_so, d_sx, d_sy, d_sl, d_sync, d_cout, d_cc, d_nslot);
 	hipLaunchKernelGGL(sketch_long_gather_kernel, dim3((unsigned)(lj.size() / 3)), dim3(64), 0, c->stream, d_jobs, d_lj, d_ch, d_cout, d_cc, d_out, d_cnt);
 	HIPCHK(ctx_sync(c));                 // (the staged tables above are read by the copies until here)
 	return WM_OK;
@@ -820,6 +891,7 @@ try {
 	if (!c || !c->d_bloom) return set_err(WM_EINVAL, "wm_index_upload has not been called on this context");
 	if (n <= 0) return WM_OK;
 	HIPCHK(hipSetDevice(c->device));
+	c->sketch_chunks = 0;
 	const int w = c->skp.w;
 	const size_t lds = (size_t)w * 64 * 12;
 	if (lds > 160 * 1024) return set_err(WM_EINVAL, "window w=%d needs %zu B of LDS per wave (max 160 KB)", w, lds);

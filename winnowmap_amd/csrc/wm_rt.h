@@ -97,6 +97,7 @@ struct wm_ctx_s {
 	hipEvent_t ev[4];
 	hipEvent_t sync_ev;                         // blocking-sync event: waiting threads sleep instead of spinning (the host cores are the scarce resource)
 	float last_ms, aux_ms;
+	int sketch_chunks;                          // wm_last_sketch_chunks: chunks the last sketch ran as wavefronts of their own (sketch_launch)
 	uint64_t acc_cells; double t_prep, t_run, t_fetch;
 	// flat index in HBM (wm_index_upload)
 	uint64_t *d_hkey, *d_hval, *d_P;

@@ -76,6 +76,12 @@ class Context:
         except Exception:
             pass
 
+    def last_sketch_chunks(self):
+        """wm_last_sketch_chunks: chunks the last sketch, window or index-sketch call on this context ran as wavefronts of their own (0: one wavefront per sequence)"""
+        lib().wm_last_sketch_chunks.argtypes = [C.c_void_p]
+        lib().wm_last_sketch_chunks.restype = C.c_int
+        return int(lib().wm_last_sketch_chunks(self._h))
+
     # ---- ksw -------------------------------------------------------------------------------------
     def ksw_batch(self, score, jobs, seqs):
         """jobs: structured array KSW_JOB_DTYPE; seqs: uint8 codes. Returns (results KSW_RES_DTYPE, cigar pool)."""
@@ -284,6 +290,14 @@ def set_even_k(on):
 def even_k_enabled():
     lib().wm_even_k_enabled.restype = C.c_int
     return bool(lib().wm_even_k_enabled())
+
+
+def set_sketch_step_chunks(on):
+    """wm_sketch_set_step_chunks: sketch long sequences chunk by chunk under -H / at an even k as well (1), or keep them on one wavefront each (0); on < 0: back
+    to what WM_SKETCH_STEP_CHUNKS in the environment says. Results never depend on it."""
+    lib().wm_sketch_set_step_chunks.argtypes = [C.c_int]
+    lib().wm_sketch_set_step_chunks.restype = None
+    lib().wm_sketch_set_step_chunks(int(on))
 
 
 def sdust_stats(reset=False):
@@ -498,7 +512,7 @@ class Index:
 
     @staticmethod
     def build_on_device(ctx, fasta, kmer_file=None, k=15, w=50, n_threads=8, hpc=False):
-        """wm_index_build_gpu[_flag]: the reference is sketched on the device (one wavefront per contig). Returns (Index, stats dict)."""
+        """wm_index_build_gpu[_flag]: the reference is sketched on the device (one wavefront per contig, per chunk of a long one). Returns (Index, stats dict)."""
         L = lib()
         _bind_map(L)
         L.wm_index_build_gpu_flag.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]
