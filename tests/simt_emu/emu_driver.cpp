@@ -378,25 +378,20 @@ int emu_seed(const uint64_t *hkey, const uint64_t *hval, const uint64_t *P, int 
 	return 0;
 }
 
-// chain DP fill: returns f, p, v
-int emu_chain_fill(int64_t n, const uint64_t *ax, const uint64_t *ay, int max_dist_x, int min_dist_x, int max_dist_y, int bw, int max_skip, int max_iter,
-                   float avg_qspan, float gap_scale, int32_t *f, int32_t *p, int32_t *v)
+// chain DP fill: returns f, p, v. W: the LDS window (a power of two >= 128); nwv = 0: chain_wave; nwv > 0, kt = 0: chain_block on nwv wavefronts;
+// kt in {1, 2, 3, 5, 10}: chain_block_wide<kt> on nwv wavefronts with kt_first tiles per wavefront in an anchor's first step (0: kt)
+int emu_chain_fill_geom(int64_t n, const uint64_t *ax, const uint64_t *ay, int max_dist_x, int min_dist_x, int max_dist_y, int bw, int max_skip, int max_iter,
+                        float avg_qspan, float gap_scale, int is_cdna, int W, int nwv, int kt, int kt_first, int32_t *f, int32_t *p, int32_t *v)
 {
+	if (W < 128 || (W & (W - 1)) || nwv < 0 || nwv > 16 || (kt != 0 && kt != 1 && kt != 2 && kt != 3 && kt != 5 && kt != 10) || nwv * kt > 128 || kt_first < 0 || kt_first > kt) return -1;
 	std::vector<wm128_t> a(n + 1);
 	for (int64_t i = 0; i < n; ++i) a[i].x = ax[i], a[i].y = ay[i];
-	wm_chain_job_t jb = { 0, (int)n, max_dist_x, min_dist_x, max_dist_y, bw, max_skip, max_iter, avg_qspan, gap_scale, 0 };
-	// test hook: bits 16.. of max_skip choose the LDS window (default 4096) so that wrap-around can be exercised on small inputs
-	int W = 4096;
-	if (max_skip >> 16) { W = max_skip >> 16; jb.max_skip &= 0xffff; }
-	if (jb.max_skip & 0x8000) { jb.is_cdna = 1; jb.max_skip &= 0x7fff; }        // test hook: bit 15 of max_skip = splice mode (src/chain.c:69-74)
-	const int kt_first_hook = (jb.max_skip >> 8) & 15;                          // test hook: bits 8..11 of max_skip = tiles per wavefront in the FIRST step of chain_block_wide (0: as many as in the others)
-	jb.max_skip &= 0xff;
+	wm_chain_job_t jb = { 0, (int)n, max_dist_x, min_dist_x, max_dist_y, bw, max_skip, max_iter, avg_qspan, gap_scale, is_cdna != 0 };
 	std::vector<int> gt(n + 1), sf(W), sp(W), stt(W);
 	std::vector<uint64_t> sx(W), sy(W);
 	simt::exec_mask() = ~0ull;
-	if (max_iter >> 24) {              // test hook: bits 24.. of max_iter = number of cooperating waves (chain_block)
-		const int NWV = max_iter >> 24, KT = (max_iter >> 20) & 15;      // bits 20..23: tiles per wavefront and step (chain_block_wide); 0 = chain_block
-		jb.max_iter &= 0xfffff;
+	if (nwv > 0) {
+		const int NWV = nwv, KT = kt, ktf = kt_first ? kt_first : kt;
 		std::vector<int> pub(NWV * (KT ? KT : 1) * 69 + 16);
 		pthread_barrier_t bar;
 		pthread_barrier_init(&bar, 0, NWV);
@@ -406,11 +401,11 @@ int emu_chain_fill(int64_t n, const uint64_t *ax, const uint64_t *ay, int max_di
 			th.emplace_back([&, w]() {
 				simt::wave_slot() = w; simt::exec_mask() = ~0ull;
 				if (KT == 0) wmk::chain_block(jb, a.data(), NWV, W, sx.data(), sy.data(), sf.data(), sp.data(), stt.data(), pub.data(), f, p, gt.data());
-				else if (KT == 1) wmk::chain_block_wide<1>(jb, a.data(), NWV, kt_first_hook ? kt_first_hook : 1, W, sx.data(), sy.data(), sf.data(), sp.data(), stt.data(), pub.data(), f, p, gt.data());
-				else if (KT == 2) wmk::chain_block_wide<2>(jb, a.data(), NWV, kt_first_hook ? kt_first_hook : 2, W, sx.data(), sy.data(), sf.data(), sp.data(), stt.data(), pub.data(), f, p, gt.data());
-				else if (KT == 3) wmk::chain_block_wide<3>(jb, a.data(), NWV, kt_first_hook ? kt_first_hook : 3, W, sx.data(), sy.data(), sf.data(), sp.data(), stt.data(), pub.data(), f, p, gt.data());
-				else if (KT == 10) wmk::chain_block_wide<10>(jb, a.data(), NWV, kt_first_hook ? kt_first_hook : 10, W, sx.data(), sy.data(), sf.data(), sp.data(), stt.data(), pub.data(), f, p, gt.data());
-				else wmk::chain_block_wide<5>(jb, a.data(), NWV, kt_first_hook ? kt_first_hook : 5, W, sx.data(), sy.data(), sf.data(), sp.data(), stt.data(), pub.data(), f, p, gt.data());
+				else if (KT == 1) wmk::chain_block_wide<1>(jb, a.data(), NWV, ktf, W, sx.data(), sy.data(), sf.data(), sp.data(), stt.data(), pub.data(), f, p, gt.data());
+				else if (KT == 2) wmk::chain_block_wide<2>(jb, a.data(), NWV, ktf, W, sx.data(), sy.data(), sf.data(), sp.data(), stt.data(), pub.data(), f, p, gt.data());
+				else if (KT == 3) wmk::chain_block_wide<3>(jb, a.data(), NWV, ktf, W, sx.data(), sy.data(), sf.data(), sp.data(), stt.data(), pub.data(), f, p, gt.data());
+				else if (KT == 10) wmk::chain_block_wide<10>(jb, a.data(), NWV, ktf, W, sx.data(), sy.data(), sf.data(), sp.data(), stt.data(), pub.data(), f, p, gt.data());
+				else wmk::chain_block_wide<5>(jb, a.data(), NWV, ktf, W, sx.data(), sy.data(), sf.data(), sp.data(), stt.data(), pub.data(), f, p, gt.data());
 			});
 		for (auto &t : th) t.join();
 		simt::block_barrier() = 0;
@@ -419,6 +414,19 @@ int emu_chain_fill(int64_t n, const uint64_t *ax, const uint64_t *ay, int max_di
 		wmk::chain_wave(jb, a.data(), W, sx.data(), sy.data(), sf.data(), sp.data(), stt.data(), f, p, gt.data());
 	for (int64_t i = 0; i < n; ++i) v[i] = p[i] >= 0 && v[p[i]] > f[i] ? v[p[i]] : f[i];   // the peak score is derived by the caller (as wm_chain_batch does)
 	return 0;
+}
+
+// the same with the geometry packed into the upper bits of two parameters (the older tests' calling convention; max_skip < 256 and max_iter < 2^20 here):
+// max_skip bits 16..: the LDS window (default 4096), bit 15: splice mode (src/chain.c:69-74), bits 8..11: tiles per wavefront in the FIRST step of
+// chain_block_wide (0: as many as in the others); max_iter bits 24..: cooperating wavefronts, bits 20..23: tiles per wavefront and step (0 = chain_block)
+int emu_chain_fill(int64_t n, const uint64_t *ax, const uint64_t *ay, int max_dist_x, int min_dist_x, int max_dist_y, int bw, int max_skip, int max_iter,
+                   float avg_qspan, float gap_scale, int32_t *f, int32_t *p, int32_t *v)
+{
+	const int W = max_skip >> 16 ? max_skip >> 16 : 4096, nwv = max_iter >> 24;
+	int kt = nwv ? (max_iter >> 20) & 15 : 0;
+	if (kt != 0 && kt != 1 && kt != 2 && kt != 3 && kt != 10) kt = 5;
+	return emu_chain_fill_geom(n, ax, ay, max_dist_x, min_dist_x, max_dist_y, bw, max_skip & 0xff, nwv ? max_iter & 0xfffff : max_iter, avg_qspan, gap_scale,
+	                           (max_skip & 0x8000) != 0, W, nwv, kt, kt ? (max_skip >> 8) & 15 : 0, f, p, v);
 }
 
 // ---- the fused window path (window_kernel.h) ----
@@ -498,6 +506,9 @@ int emu_win_extract(int n, uint64_t *ax, uint64_t *ay, const int32_t *f_in, cons
 	return res.n_v;
 }
 
+static int g_win_small_cdna = 0;
+void emu_win_small_set_cdna(int is_cdna) { g_win_small_cdna = is_cdna != 0; }      // splice mode of the emu_win_small calls that follow
+
 // a small job from its unsorted anchors to its chains by one wavefront in LDS (win_small_wave): n_pre handed-in anchors first; seeded != 0: the job
 // has a sequence (its seeded part is sorted, then the union). Returns n_v; chains in u_out, chained anchors in ax / ay
 int emu_win_small(int n, int n_pre, int seeded, uint64_t *ax, uint64_t *ay, int max_dist_x, int min_dist_x, int max_dist_y, int bw, int max_skip, int max_iter,
@@ -511,7 +522,7 @@ int emu_win_small(int n, int n_pre, int seeded, uint64_t *ax, uint64_t *ay, int 
 	wm_win_job_t jb;
 	memset(&jb, 0, sizeof(jb));
 	jb.seq_off = seeded ? 0 : -1; jb.n_pre = n_pre; jb.max_dist_x = max_dist_x; jb.min_dist_x = min_dist_x; jb.max_dist_y = max_dist_y; jb.bw = bw;
-	jb.max_skip = max_skip; jb.max_iter = max_iter; jb.min_cnt = min_cnt; jb.min_sc = min_sc; jb.gap_scale = gap_scale;
+	jb.max_skip = max_skip; jb.max_iter = max_iter; jb.min_cnt = min_cnt; jb.min_sc = min_sc; jb.gap_scale = gap_scale; jb.is_cdna = g_win_small_cdna;
 	uint64_t ctr[2] = { 0, 0 };
 	wm_win_res_t res;
 	memset(&res, 0, sizeof(res));

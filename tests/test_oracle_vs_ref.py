@@ -244,6 +244,19 @@ def test_chain_vs_reference(ref_index):
             assert np.array_equal(ou, ru) and np.array_equal(obx, rbx) and np.array_equal(oby, rby)
 
 
+def test_chain_edge_cases_vs_reference():
+    """the oracle's mm_chain_dp equals the reference's on every case of tests/chaincases.py — class sizes, density edges, every chain parameter at its
+    limits, hand-placed score edges — under the case's own min_cnt / min_sc and under the open observer: what the emulator and GPU tests of the chain
+    fill expect (tests/test_chain_edges_emu.py, tests/test_chain_edges_gpu.py) is what the reference computes"""
+    _need_ref()
+    import chaincases
+    for c in chaincases.all_cases():
+        for p in chaincases.observers(c["par"]):
+            ou, obx, oby = W.o_chain_dp(c["x"], c["y"], **p)
+            ru, rbx, rby = W.r_chain_dp(c["x"], c["y"], **p)
+            assert np.array_equal(ou, ru) and np.array_equal(obx, rbx) and np.array_equal(oby, rby), (c["name"], p["min_cnt"], p["min_sc"])
+
+
 def test_exts2_oracle_vs_reference():
     """wmo_ksw_exts2 (oracle/wm_oracle.c) against the reference's own ksw_exts2_sse (src/ksw2_exts2_sse.c) on transcript-like inputs: every
     splice flag, left / right gap alignment, approximate and exact maximum, extension-only, reversed operands, junction annotation, N."""

@@ -156,6 +156,10 @@ WM_DEV V<int> ilog2_pos(V<int> v) { return V<int>(31) - vclz(v | 1); }
 // which the reference may still visit when min_dist_x relaxes max_iter inside dense repeats (src/chain.c:51-55) — are
 // served from global memory (L1-bypassing loads; marks for them go to gt). For n <= W nothing ever leaves the window.
 // The peak score v[] (src/chain.c:89) is a function of f and p only and is not needed by the fill: the caller derives it.
+// STATUS (chain_wave, W = 256 / 1024 and the wrapping window): compared bit for bit with the oracle — which tests/test_oracle_vs_ref.py pins to the reference on
+// the same cases — on the wavefront emulator and on the GPU at the class sizes (1 .. 4160 anchors, full and partial flush tiles), with max_skip 0 .. 1000,
+// max_iter 0 .. 5000 around the 64-lane tile, min_dist_x 0 .. max_dist_x, gap scales, the splice cost, bw = 0, max_dist_y = 0 and hand-placed score
+// edges (tests/chaincases.py, tests/test_chain_edges_emu.py, tests/test_chain_edges_gpu.py).
 
 // advance st over the sorted x: the two scalar loops of src/chain.c:50-55, 64 candidates per LDS round trip
 WM_DEV long long chain_advance_st(long long st, long long i, uint64_t ri, uint64_t dist, long long keep_iter /* <0: no iteration clause */,
@@ -499,6 +503,10 @@ WM_DEV void chain_block(const wm_chain_job_t jb, const wm128_t *anchor_pool, int
 // anchor, profiles/r06_chain_fill_probe.txt), but the 5-Mb contigs of BASELINE config 5 scan their whole window: 28.8 s with kt_first = 1 against 20.0 s
 // with kt_first = KT (profiles/r06_closure.jsonl) — so the callers pass KT unless WM_CHAIN_WIDE_FIRST says otherwise.
 // pub: NT * 69 ints (tile maxima | I lo,hi,M lo,hi per tile | 64 scores per tile, written only by tiles that have an improvement), NT = NWV * KT <= 128.
+// STATUS: compared bit for bit with the oracle on the wavefront emulator and on the GPU at 16 x 5, 8 x 10 and 16 x 3 tiles, with kt_first = 1 and KT, on the dense
+// cases of tests/chaincases.py: every chain parameter at its limits, windows of more than NWV * KT * 64 predecessors (a second and a third step), breaks
+// that fall on marks in the global slab, windows cut by max_iter at 63 / 64 / 65 / 300 / 5000 (tests/test_chain_edges_emu.py, tests/test_chain_edges_gpu.py;
+// the latter also runs chain_block, WM_CHAIN_WIDE=0, in a process of its own).
 // ------------------------------------------------------------------------------------------------------
 template <int KT>
 WM_DEV void chain_block_wide(const wm_chain_job_t jb, const wm128_t *anchor_pool, int NWV, int kt_first, int W, uint64_t *sx, uint64_t *sy, int *sf, int *sp, int *st_,

@@ -424,6 +424,9 @@ WM_DEV float win_avg_qspan(const wm128_t *a_, int n)
 	return (float)(uint64_t)(uint32_t)sum / (float)(long long)n;
 }
 
+// STATUS (win_plan_wave): the class rule below is restated in tests/chaincases.py (klass_window; wm_chain_batch's rule, which lacks the second clause, next to
+// it) and pinned at both thresholds — worst = 900 / 901, 7 / 8 sample points over 128 — on the emulator (tests/test_chain_edges_emu.py); the GPU runs the
+// same cases through wm_window_batch with each job's own parameters (tests/test_chain_edges_gpu.py).
 WM_DEV void win_plan_wave(const wm_win_job_t jb, int j, uint64_t a_off, int n, const wm128_t *a_, wm_chain_job_t *cj, int *lists, int *counts, int n_jobs)
 {
 	const V<int> ln = lane();
