@@ -78,6 +78,11 @@ typedef struct {
 	uint32_t cig_off;
 } wm_ksw_result_t;
 
+/* The longest target any alignment entry point takes (wm_ksw_batch, wm_ksw_batch_pos, wm_ksw_batch_pos_zd, wm_ksw_dev_prepare, wm_ksw_extd2,
+ * wm_ksw_exts2_batch): the kernels' exact-maximum reduction carries the target lane in 28 bits (csrc/ksw_kernel.h, ksw_pri_pack). A job with a
+ * longer target is refused with WM_EINVAL; the reference has no such limit (and no use for one: 2^28 rows of traceback). */
+#define WM_KSW_MAX_TLEN (1 << 28)
+
 /* seqs: host buffer with all query/target codes of the batch. results[n_jobs] and cigar_pool
  * (capacity cigar_cap ops) are host buffers filled on return; *cigar_used receives the ops written.
  * Returns WM_ENOMEM if cigar_cap is too small (then *cigar_used holds the required size). */
@@ -314,6 +319,9 @@ int wm_sdust_batch(wm_ctx_t *ctx, int n, const uint8_t *seqs, size_t seqs_bytes,
 /* process-wide account of the filter since the last reset: out5 = window calls that ran it, milliseconds of its kernel, jobs of those calls, jobs the host
  * finished, largest list of perfect intervals seen */
 void wm_sdust_stats(double *out5, int reset);
+/* process-wide account of splice mode's alignment calls since the last reset: out2 = calls of the mapper's exts2 operation that held requests, and the groups
+ * those calls were split into so that each group's unbanded traceback fits 0.6 of its context's arena (one wm_ksw_exts2_batch per group) */
+void wm_exts2_stats(uint64_t *out2, int reset);
 /* kernel time of the last sketch/seed/chain/window batch call (HIP events on the context stream), ms */
 float wm_last_aux_ms(const wm_ctx_t *ctx);
 /* Sequences of WM_SKETCH_LONG (65 536) codes and more are sketched in chunks of WM_SKETCH_CHUNK (16 384) positions, one wavefront per chunk, by

@@ -223,16 +223,21 @@ int emu_ksw_dual(int nc, int has_b, const int32_t *qlen, const int32_t *tlen, co
 	}
 	return 0;
 }
+// the lane priority of the exact-maximum reduction (ksw_kernel.h): scalar and vector form of the pack, and the unpack
+int emu_ksw_pri_pack(int grp, int t) { return wmk::ksw_pri_pack(grp, t); }
+int emu_ksw_pri_pack_v(int grp, int t) { simt::exec_mask() = ~0ull; return simt::readlane(wmk::ksw_pri_pack(simt::V<int>(grp), simt::V<int>(t)), 0); }
+int emu_ksw_pri_lane(int pri) { return wmk::ksw_pri_lane(pri); }
 void emu_set_coop_backtrack(int on) { g_coop_backtrack = on; }       // 1: ksw_backtrack_wave instead of ksw_backtrack_thread
 
 
-// ksw_exts2_sse through the emulated splice kernel + its backtrack; junc may be null
+// ksw_exts2_sse through the emulated splice kernel + its backtrack; junc may be null. -2: a scoring set wm_ksw_exts2_batch refuses (ksw_plan.h)
 int emu_ksw_exts2(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const int8_t *mat, int q, int e, int q2, int noncan, int zdrop,
                   int junc_bonus, int flag, const uint8_t *junc, int32_t *ez_out, uint32_t *cigar_out, int cigar_cap)
 {
 	wm_ksw_score_t sc;
 	memset(&sc, 0, sizeof(sc));
 	sc.match = mat[0]; sc.mismatch = mat[1]; sc.sc_ambi = mat[24]; sc.q = (int8_t)q; sc.e = (int8_t)e; sc.q2 = (int8_t)q2; sc.e2 = 0;
+	if (wm_ksw_exts2_score_check(&sc)) return -2;
 	std::vector<uint8_t> seqs((size_t)qlen + tlen + 64, 0), jn;
 	memcpy(seqs.data(), query, qlen); memcpy(seqs.data() + qlen, target, tlen);
 	if (junc) { jn.assign((size_t)qlen + tlen + 64, 0); memcpy(jn.data() + qlen, junc, tlen); }

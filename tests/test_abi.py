@@ -134,3 +134,14 @@ def test_round4_entry_points_refuse_bad_arguments_without_touching_a_device(lib)
     lib.wm_set_cmdline.argtypes = [C.c_int, C.c_void_p]
     lib.wm_set_cmdline(-1, None)
     lib.wm_set_cmdline(0, None)
+
+
+def test_exts2_stats_is_a_process_wide_account(lib):
+    """wm_exts2_stats (calls and groups of the mapper's splice-mode alignment operation) answers without a device, and resets"""
+    out = np.full(2, 7, np.uint64)
+    lib.wm_exts2_stats.argtypes = [C.c_void_p, C.c_int]
+    lib.wm_exts2_stats.restype = None
+    lib.wm_exts2_stats(out.ctypes.data, 1)
+    lib.wm_exts2_stats(out.ctypes.data, 0)
+    assert out.tolist() == [0, 0] and gpu.exts2_stats() == {"calls": 0, "groups": 0}
+    lib.wm_exts2_stats(None, 0)

@@ -273,3 +273,27 @@ def test_exts2_oracle_vs_reference():
         assert np.array_equal(o["cigar"], r["cigar"]), (hex(c["flag"]), W.cigar_str(o["cigar"]), W.cigar_str(r["cigar"]))
         n_intron += any((int(x) & 0xf) == 3 for x in o["cigar"])
     assert n_intron > 100, n_intron                      # the cases do exercise the intron state
+
+
+def test_exts2_edge_cases_oracle_vs_reference():
+    """every case of tests/exts2cases.py (shapes at the lane boundaries, signals at the first and last admitted position, junction bits, int8 wrap, the long-gap
+    schedule, ties, z-drop, scoring sets on the limit): wmo_ksw_exts2 against the reference's own ksw_exts2_sse; the scoring sets the reference refuses give a
+    reset result in both"""
+    _need_ref()
+    import exts2cases as XC
+    cases = XC.edge_cases()
+    c0 = next(c for c in cases if c["name"].startswith("limit_ambi_at_limit"))
+    cases += [dict(c0, name="rejected_" + nm, a=a, b=b, q_=q, e=e, q2=q2, sc_ambi=amb) for nm, (a, b, q, e, q2, amb) in XC.REJECTED]
+    n_reset = 0
+    for c in cases:
+        kw = dict(mat=W.simple_mat(c["a"], c["b"], c["sc_ambi"]), q=c["q_"], e=c["e"], q2=c["q2"], noncan=c["noncan"], zdrop=c["zdrop"],
+                  junc_bonus=c["junc_bonus"], flag=c["flag"], junc=c["junc"])
+        o = W.o_ksw_exts2(c["q"], c["t"], **kw)
+        r = W.r_ksw_exts2(c["q"], c["t"], **kw)
+        for k in W.EZ_FIELDS:
+            assert o[k] == r[k], (c["name"], k, o[k], r[k])
+        assert np.array_equal(o["cigar"], r["cigar"]), (c["name"], W.cigar_str(o["cigar"])[:60], W.cigar_str(r["cigar"])[:60])
+        if c["name"].startswith("rejected_"):
+            assert [r[k] for k in W.EZ_FIELDS] == [0, 0, -1, -1, -0x40000000, -1, -0x40000000, -1, -0x40000000, 0] and len(r["cigar"]) == 0, c["name"]
+            n_reset += 1
+    assert n_reset == len(XC.REJECTED)

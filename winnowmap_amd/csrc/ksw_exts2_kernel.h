@@ -159,7 +159,7 @@ WM_DEV void ksw_dp_exts2(const wm_ksw_score_t sc, int noncan, int junc_bonus, co
 					const vbool inb = t >= st0 && t <= en0;
 					WM_IF(inb) st32<COH>(Hm, t, hn); WM_END
 					V<int> grp = sel(t == en0, 5, sel(t < en1, 4 - ((t - st0) & 3), 0));
-					V<int> pri = (grp << 20) | (0xfffff - t);
+					V<int> pri = ksw_pri_pack(grp, t);
 					V<long long> k = cast<long long>(hn) * 4294967296LL + cast<long long>(pri);
 					key = sel(inb && k > key, k, key);
 				}
@@ -167,7 +167,7 @@ WM_DEV void ksw_dp_exts2(const wm_ksw_score_t sc, int noncan, int junc_bonus, co
 					WM_IF(t == 0)
 						const V<int> h0 = (nv >> 24) - qe;
 						st32<COH>(Hm, t, h0);
-						key = cast<long long>(h0) * 4294967296LL + (long long)((5 << 20) | 0xfffff);
+						key = cast<long long>(h0) * 4294967296LL + (long long)ksw_pri_pack(5, 0);
 					WM_END
 				}
 			WM_END
@@ -177,7 +177,7 @@ WM_DEV void ksw_dp_exts2(const wm_ksw_score_t sc, int noncan, int junc_bonus, co
 			key = wave_max_i64(key);
 			const long long kk = uniform(key);
 			const int max_H = (int)(kk >> 32), pri = (int)(kk & 0xffffffffLL);
-			const int max_t = 0xfffff - (pri & 0xfffff);
+			const int max_t = ksw_pri_lane(pri);
 			if (en0 == tlen - 1) { const int h = ld32s<COH>(Hm, en0); if (h > ez_mte) ez_mte = h, ez_mte_q = r - en; }
 			if (r - st0 == qlen - 1) { const int h = ld32s<COH>(Hm, st0); if (h > ez_mqe) ez_mqe = h, ez_mqe_t = st0; }
 			if (max_H > ez_max) {

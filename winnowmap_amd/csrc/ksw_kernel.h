@@ -43,6 +43,18 @@ using namespace simt;
 // value (int8 semantics) -> top-byte representation
 WM_DEV int tb8(int v) { return (int)((unsigned)v << 24); }
 
+// The lane priority of the exact-maximum reduction, shared by every ksw kernel. The reference's SIMD tie rule (src/ksw2_extd2_sse.c:315-358,
+// src/ksw2_exts2_sse.c:345-371) picks, among the lanes of a row that hold the maximum H, lane en0 first (group 5), then the residue groups of
+// [st0, en1) (4 .. 1), then the tail (0); inside a group the lowest lane. As one integer under H: the group above KSW_PRI_TBITS bits of
+// (mask - t), so that greater H wins first, then the greater group, then the smaller t. Groups are 0 .. 5: the value stays below 2^31 (the
+// 32-bit reductions of ksw_packed_kernel.h and its kin take signed maxima, with -1 for "no lane"). t must be below WM_KSW_MAX_TLEN (include/wm_gpu.h): every entry
+// point rejects longer targets (wm_ksw.hip).
+#define KSW_PRI_TBITS 28
+#define KSW_PRI_TMASK ((1 << KSW_PRI_TBITS) - 1)
+static_assert(WM_KSW_MAX_TLEN - 1 == KSW_PRI_TMASK, "include/wm_gpu.h documents the limit");
+template <class T> WM_DEV T ksw_pri_pack(T grp, T t) { return (grp << KSW_PRI_TBITS) | (T(KSW_PRI_TMASK) - t); }
+WM_DEV int ksw_pri_lane(int pri) { return KSW_PRI_TMASK - (pri & KSW_PRI_TMASK); }
+
 // read lane t (uniform) of a per-thread register array: thread (t-base)/B, register (t-base)%B
 template <int B> WM_DEV int get_lane(const V<int> (&a)[B], int base, int t)
 {
@@ -182,7 +194,7 @@ WM_DEV void ksw_dp_generic(const wm_ksw_score_t sc, const wm_ksw_djob_t jb, cons
 					const vbool inb = t >= st0 && t <= en0;
 					WM_IF(inb) st32<COH>(Hm, t, hn); WM_END
 					V<int> grp = sel(t == en0, 5, sel(t < en1, 4 - ((t - st0) & 3), 0));
-					V<int> pri = (grp << 20) | (0xfffff - t);
+					V<int> pri = ksw_pri_pack(grp, t);
 					V<long long> k = cast<long long>(hn) * 4294967296LL + cast<long long>(pri);
 					key = sel(inb && k > key, k, key);
 				}
@@ -190,7 +202,7 @@ WM_DEV void ksw_dp_generic(const wm_ksw_score_t sc, const wm_ksw_djob_t jb, cons
 					WM_IF(t == 0)
 						const V<int> h0 = (nv >> 24) - qe;
 						st32<COH>(Hm, t, h0);
-						key = cast<long long>(h0) * 4294967296LL + (long long)((5 << 20) | 0xfffff);
+						key = cast<long long>(h0) * 4294967296LL + (long long)ksw_pri_pack(5, 0);
 					WM_END
 				}
 			WM_END
@@ -200,7 +212,7 @@ WM_DEV void ksw_dp_generic(const wm_ksw_score_t sc, const wm_ksw_djob_t jb, cons
 			key = wave_max_i64(key);
 			const long long kk = uniform(key);
 			const int max_H = (int)(kk >> 32), pri = (int)(kk & 0xffffffffLL);
-			const int max_t = 0xfffff - (pri & 0xfffff);
+			const int max_t = ksw_pri_lane(pri);
 			if (en0 == tlen - 1) { const int h = ld32s<COH>(Hm, en0); if (h > ez_mte) ez_mte = h, ez_mte_q = r - en; }
 			if (r - st0 == qlen - 1) { const int h = ld32s<COH>(Hm, st0); if (h > ez_mqe) ez_mqe = h, ez_mqe_t = st0; }
 			if (max_H > ez_max) {
@@ -410,7 +422,7 @@ WM_DEV void ksw_dp_block(const wm_ksw_score_t sc, const wm_ksw_djob_t jb, const 
 				if (!approx) {
 					const V<int> hn = oh[k] + (nv >> 24);
 					gst(Hm, t & wmask, hn);
-					const V<int> pri = ((4 - ((t - st0) & 3)) << 20) | (0xfffff - t);
+					const V<int> pri = ksw_pri_pack(V<int>(4 - ((t - st0) & 3)), t);
 					const V<long long> kk = cast<long long>(hn) * 4294967296LL + cast<long long>(pri);
 					key = sel(kk > key, kk, key);
 				}
@@ -457,7 +469,7 @@ WM_DEV void ksw_dp_block(const wm_ksw_score_t sc, const wm_ksw_djob_t jb, const 
 							WM_IF(t == st0) gst(pub_val, V<int>(1), hn); WM_END
 						WM_END
 						V<int> grp = sel(t == en0, 5, sel(t < en1, 4 - ((t - st0) & 3), 0));
-						V<int> pri = (grp << 20) | (0xfffff - t);
+						V<int> pri = ksw_pri_pack(grp, t);
 						V<long long> kk = cast<long long>(hn) * 4294967296LL + cast<long long>(pri);
 						key = sel(inb && kk > key, kk, key);
 					} else {
@@ -465,7 +477,7 @@ WM_DEV void ksw_dp_block(const wm_ksw_score_t sc, const wm_ksw_djob_t jb, const 
 							const V<int> h0 = (nv >> 24) - qe;
 							hkeep = h0;
 							gst(pub_val, V<int>(0), h0); gst(pub_val, V<int>(1), h0);
-							key = cast<long long>(h0) * 4294967296LL + (long long)((5 << 20) | 0xfffff);
+							key = cast<long long>(h0) * 4294967296LL + (long long)ksw_pri_pack(5, 0);
 						WM_END
 					}
 					gst(Hm, t & wmask, hkeep);
@@ -491,7 +503,7 @@ WM_DEV void ksw_dp_block(const wm_ksw_score_t sc, const wm_ksw_djob_t jb, const 
 				if (k2 > kk) kk = k2;
 			}
 			const int max_H = (int)(kk >> 32), pri = (int)(kk & 0xffffffffLL);
-			const int max_t = 0xfffff - (pri & 0xfffff);
+			const int max_t = ksw_pri_lane(pri);
 			if (en0 == tlen - 1) { const int h = gld(pub_val, 0LL); if (h > ez_mte) ez_mte = h, ez_mte_q = r - en; }
 			if (r - st0 == qlen - 1) { const int h = gld(pub_val, 1LL); if (h > ez_mqe) ez_mqe = h, ez_mqe_t = st0; }
 			if (max_H > ez_max) {

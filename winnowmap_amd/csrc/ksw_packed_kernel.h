@@ -418,7 +418,7 @@ WM_DEV void ksw_dp_packed(const wm_ksw_score_t sc, const wm_ksw_djob_t jb, const
 					// then the tail [en1, en0); inside a group the lower lane. Chunk starts are multiples of 4, so the residue is the same in every chunk.
 					// Chunks that do not hold the maximum cost one compare and a branch; no per-chunk scalar bookkeeping.
 					const int en1 = st0 + (en0 - st0) / 4 * 4;
-					const V<int> g4 = (4 - ((ln + (base - st0)) & 3)) << 20;
+					const V<int> g4 = 4 - ((ln + (base - st0)) & 3);
 					V<int> best = -1;
 					static_for_desc<B>([&](auto CC) {
 						constexpr int ci = decltype(CC)::value;
@@ -427,12 +427,11 @@ WM_DEV void ksw_dp_packed(const wm_ksw_score_t sc, const wm_ksw_djob_t jb, const
 						const vbool hit = H[ci] == max_H && cast<unsigned>(t - st0) <= (unsigned)(en0 - st0);
 						if (any(hit)) {
 							WM_KEEP_BRANCH();
-							V<int> pri = sel(t < en1, g4, V<int>(0));
-							pri = sel(t == en0, V<int>(5 << 20), pri) | (V<int>(0xfffff) - t);
+							const V<int> pri = ksw_pri_pack(sel(t == en0, V<int>(5), sel(t < en1, g4, V<int>(0))), t);
 							best = vmax(best, sel(hit, pri, V<int>(-1)));
 						}
 					});
-					max_t = 0xfffff - (wave_max_i32(best) & 0xfffff);
+					max_t = ksw_pri_lane(wave_max_i32(best));
 				}
 			} else {
 				WM_IF(ln == 0) H[0] = vlo8(Vv[0]) - qe; WM_END

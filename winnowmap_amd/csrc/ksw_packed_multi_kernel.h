@@ -308,7 +308,7 @@ WM_DEV void ksw_dp_pmulti(const wm_ksw_score_t sc, const wm_ksw_djob_t jb, const
 					if (hm > ez_max || (zdrop >= 0 && ez_max - hm > zdrop)) {
 						WM_KEEP_BRANCH();
 						const int en1 = st0 + (en0 - st0) / 4 * 4;
-						const V<int> g4 = (4 - ((ln + (base - st0)) & 3)) << 20;
+						const V<int> g4 = 4 - ((ln + (base - st0)) & 3);
 						V<int> best = -1;
 #pragma unroll
 						for (int ci = 0; ci < 2 * BP; ++ci) {
@@ -318,8 +318,7 @@ WM_DEV void ksw_dp_pmulti(const wm_ksw_score_t sc, const wm_ksw_djob_t jb, const
 							const vbool hit = H[ci] == hm && cast<unsigned>(t - st0) <= (unsigned)(en0 - st0);
 							if (any(hit)) {
 								WM_KEEP_BRANCH();
-								V<int> pri = sel(t < en1, g4, V<int>(0));
-								pri = sel(t == en0, V<int>(5 << 20), pri) | (V<int>(0xfffff) - t);
+								const V<int> pri = ksw_pri_pack(sel(t == en0, V<int>(5), sel(t < en1, g4, V<int>(0))), t);
 								best = vmax(best, sel(hit, pri, V<int>(-1)));
 							}
 						}
@@ -329,7 +328,7 @@ WM_DEV void ksw_dp_pmulti(const wm_ksw_score_t sc, const wm_ksw_djob_t jb, const
 				}
 			} else if (wv == 0) {
 				WM_IF(ln == 0) H[0] = vlo8(Vv[0]) - qe; WM_END
-				kk = (long long)readlane(H[0], 0) * 4294967296LL + (long long)((5 << 20) | 0xfffff);
+				kk = (long long)readlane(H[0], 0) * 4294967296LL + (long long)ksw_pri_pack(5, 0);
 			}
 			int slot, half, thr;
 			if (owner(en0, slot, half, thr) == wv) {
@@ -360,7 +359,7 @@ WM_DEV void ksw_dp_pmulti(const wm_ksw_score_t sc, const wm_ksw_djob_t jb, const
 				if (k2 > kk) kk = k2;
 			}
 			const int max_H = (int)(kk >> 32), pri = (int)(kk & 0xffffffffLL);
-			const int max_t = 0xfffff - (pri & 0xfffff);
+			const int max_t = ksw_pri_lane(pri);
 			if (en0 == tlen - 1) { const int h = gld(pubr, (long long)(2 * NWV)); if (h > ez_mte) ez_mte = h, ez_mte_q = r - en; }
 			if (r - st0 == qlen - 1) { const int h = gld(pubr, (long long)(2 * NWV + 1)); if (h > ez_mqe) ez_mqe = h, ez_mqe_t = st0; }
 			if (max_H > ez_max) {

@@ -126,6 +126,18 @@ static inline int wm_ksw_classify(int qlen, int tlen, int w, int has_n, int flag
 }
 
 // parameter ranges the kernels support (everything the reference's mm_check_opt admits, src/options.c:166-176)
+// The scoring sets wm_ksw_exts2_batch takes: those with which ksw_exts2_sse aligns at all. It returns a reset ksw_extz_t for q2 <= q + e
+// (src/ksw2_exts2_sse.c:66) and when the lowest score of the whole matrix, the N score included (sc_ambi == 0 means -e, :74), is below -2 (q + e) (:80-84).
+// 0 = fine, else which rule refuses the set.
+static inline int wm_ksw_exts2_score_check(const wm_ksw_score_t *sc)
+{
+	if (sc->e <= 0 || sc->q2 <= sc->q + sc->e) return 1;
+	if (-(int)sc->mismatch > 2 * (sc->q + sc->e)) return 2;
+	const int n_sc = sc->sc_ambi == 0 ? -sc->e : sc->sc_ambi;
+	if (-n_sc > 2 * (sc->q + sc->e)) return 3;
+	return 0;
+}
+
 static inline int wm_ksw_score_ok(const wm_ksw_score_t *sc)
 {
 	if (sc->match <= 0 || sc->mismatch >= 0 || sc->sc_ambi > 0) return 0;

@@ -498,7 +498,7 @@ WM_DEV void ksw_dp_stripe(const wm_ksw_score_t sc, const wm_ksw_djob_t jb, const
 								if (safe || hm > ezl || (zdrop >= 0 && ezl + ez_slack - hm > zdrop)) {
 									WM_KEEP_BRANCH();
 									const int en1 = st0 + (en0 - st0) / 4 * 4;
-									const V<int> g4 = (4 - ((ln + (a - st0)) & 3)) << 20;    // (a, chunk starts: multiples of 4 — the residue is the same in every chunk)
+									const V<int> g4 = 4 - ((ln + (a - st0)) & 3);    // (a, chunk starts: multiples of 4 — the residue is the same in every chunk)
 									V<int> best = -1;
 									static_for_desc<B>([&](auto CC) {
 										constexpr int ci = decltype(CC)::value;
@@ -507,8 +507,7 @@ WM_DEV void ksw_dp_stripe(const wm_ksw_score_t sc, const wm_ksw_djob_t jb, const
 										const vbool hit = H[ci] == hm && cast<unsigned>(t - st0) <= (unsigned)(en0 - st0);
 										if (any(hit)) {
 											WM_KEEP_BRANCH();
-											V<int> pri = sel(t < en1, g4, V<int>(0));
-											pri = sel(t == en0, V<int>(5 << 20), pri) | (V<int>(0xfffff) - t);
+											const V<int> pri = ksw_pri_pack(sel(t == en0, V<int>(5), sel(t < en1, g4, V<int>(0))), t);
 											best = vmax(best, sel(hit, pri, V<int>(-1)));
 										}
 									});
@@ -520,12 +519,12 @@ WM_DEV void ksw_dp_stripe(const wm_ksw_score_t sc, const wm_ksw_djob_t jb, const
 							}
 						} else if (a == 0) {                                         // row 0: one cell (:346)
 							WM_IF(ln == 0) H[0] = vlo8(Vv[0]) - qe; WM_END
-							pm = readlane(H[0], 0); ppri = (5 << 20) | 0xfffff;
+							pm = readlane(H[0], 0); ppri = ksw_pri_pack(5, 0);
 							h_en0 = pm;
 						}
 						if (r - st0 == qlen - 1 && st0 >= a && st0 < a + SW) hst0 = h_of(st0);
 						if (is_last) {
-							const int max_H = pm, max_t = 0xfffff - (ppri & 0xfffff);
+							const int max_H = pm, max_t = ksw_pri_lane(ppri);
 							if (en0 == tlen - 1) { if (h_en0 > ez_mte) ez_mte = h_en0, ez_mte_q = r - en; }
 							if (r - st0 == qlen - 1) { if (hst0 > ez_mqe) ez_mqe = hst0, ez_mqe_t = st0; }
 							if (max_H > ez_max) {

@@ -458,7 +458,7 @@ static int ksw_prepare_impl(wm_ctx_t *c, const wm_ksw_score_t *sc_in, int n_jobs
 	const bool never = -min_sc > 2 * (sc.q + sc.e);
 	uint64_t tb_off = 0, cig_off = 0;
 	std::vector<uint64_t> cells(n_jobs, 0), bands(n_jobs, 0);
-	std::atomic<int> bad(-1);
+	std::atomic<int> bad(-1), bad_len(-1);
 	WM_SITE("ksw.classify");
 	wm::parallel_for(c->host_threads, (size_t)n_jobs, [&](size_t i) {          // per-job classification (byte jobs: scans both sequences for N)
 		wm_ksw_djob_t &d = b->jobs[i];
@@ -469,6 +469,7 @@ static int ksw_prepare_impl(wm_ctx_t *c, const wm_ksw_score_t *sc_in, int n_jobs
 		memset(&d, 0, sizeof(d));
 		d.qlen = qlen; d.tlen = tlen; d.w = w; d.zdrop = zdrop; d.end_bonus = end_bonus; d.flag = flag;
 		if (flag & (0x01 | 0x04 | 0x10 | 0x100 | 0x200 | 0x400)) { bad = (int)i; d.klass = -1; return; }
+		if (tlen > WM_KSW_MAX_TLEN) { bad_len = (int)i; d.klass = -1; return; }                                         // ksw_pri_pack (ksw_kernel.h)
 		if (qlen <= 0 || tlen <= 0 || never) { d.klass = -1; return; }                                                 // :68,:92
 		const int has_n = pos ? (pos[i].has_n != 0) : (wm_ksw_has_n(seqs + q_off, qlen) | wm_ksw_has_n(seqs + t_off, tlen));
 		d.q_off = pos ? q_off : (uint32_t)(q_off - slab_lo); d.t_off = pos ? t_off : (uint32_t)(t_off - slab_lo);
@@ -488,6 +489,11 @@ static int ksw_prepare_impl(wm_ctx_t *c, const wm_ksw_score_t *sc_in, int n_jobs
 		const int i = bad;
 		delete b;
 		return set_err(WM_EINVAL, "job %d: KSW_EZ_SCORE_ONLY/GENERIC_SC/APPROX_DROP/SPLICE flags are not used by the mapper (src/align.c) and not supported", i);
+	}
+	if (bad_len >= 0) {
+		const int i = bad_len;
+		delete b;
+		return set_err(WM_EINVAL, "job %d: target longer than WM_KSW_MAX_TLEN = %d bases (the exact-maximum reduction carries the target lane in 28 bits)", i, WM_KSW_MAX_TLEN);
 	}
 	for (int i = 0; i < n_jobs; ++i) {
 		wm_ksw_djob_t &d = b->jobs[i];
@@ -1061,8 +1067,10 @@ try {
 	if (n_jobs == 0) return WM_OK;
 	if (!sc_in || !jobs || !seqs || !results) return set_err(WM_EINVAL, "null argument");
 	const wm_ksw_score_t sc = *sc_in;
-	if (sc.e <= 0 || sc.q2 <= sc.q + sc.e) return set_err(WM_EINVAL, "ksw_exts2 needs e > 0 and q2 > q + e (src/ksw2_exts2_sse.c:66)");
-	if (-(int)sc.mismatch > 2 * (sc.q + sc.e)) return set_err(WM_EINVAL, "mismatch penalty above 2 (q + e): the reference returns without aligning (src/ksw2_exts2_sse.c:84)");
+	const int sc_bad = wm_ksw_exts2_score_check(&sc);              // ksw_plan.h: the reference's early returns
+	if (sc_bad == 1) return set_err(WM_EINVAL, "ksw_exts2 needs e > 0 and q2 > q + e (src/ksw2_exts2_sse.c:66)");
+	if (sc_bad == 2) return set_err(WM_EINVAL, "mismatch penalty above 2 (q + e): the reference returns without aligning (src/ksw2_exts2_sse.c:84)");
+	if (sc_bad == 3) return set_err(WM_EINVAL, "N score below -2 (q + e): the reference returns without aligning (src/ksw2_exts2_sse.c:84)");
 	if (noncan < -127 || noncan > 127 || junc_bonus < -127 || junc_bonus > 127) return set_err(WM_EINVAL, "noncan / junc_bonus are int8 in the reference");
 	HIPCHK(hipSetDevice(c->device));
 	ArenaMark mark(c);
@@ -1072,6 +1080,7 @@ try {
 	for (int i = 0; i < n_jobs; ++i) {
 		const wm_ksw_job_t &jb = jobs[i];
 		if (jb.qlen <= 0 || jb.tlen <= 0) return set_err(WM_EINVAL, "job %d: empty operand", i);
+		if (jb.tlen > WM_KSW_MAX_TLEN) return set_err(WM_EINVAL, "job %d: target longer than WM_KSW_MAX_TLEN = %d bases (the exact-maximum reduction carries the target lane in 28 bits)", i, WM_KSW_MAX_TLEN);
 		if ((uint64_t)jb.q_off + jb.qlen > seqs_bytes || (uint64_t)jb.t_off + jb.tlen > seqs_bytes) return set_err(WM_EINVAL, "job %d: operands outside seqs", i);
 		if (jb.flag & (0x01 | 0x04 | 0x10)) return set_err(WM_EINVAL, "job %d: KSW_EZ_SCORE_ONLY / GENERIC_SC / APPROX_DROP are not supported", i);
 		wm_ksw_djob_t &d = dj[i];

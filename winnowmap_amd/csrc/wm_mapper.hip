@@ -18,6 +18,15 @@
 #include "host/wm_kmers.cpp"
 #include "host/wm_pipeline.cpp"
 
+// process-wide account of splice mode's alignment calls (wm_exts2_stats): calls of GpuOpsCtx::exts2_batch that held requests, and the groups they were
+// split into (one wm_ksw_exts2_batch each)
+static std::atomic<uint64_t> g_exts2_calls{0}, g_exts2_groups{0};
+extern "C" void wm_exts2_stats(uint64_t *out2, int reset)
+{
+	if (out2) { out2[0] = g_exts2_calls.load(); out2[1] = g_exts2_groups.load(); }
+	if (reset) { g_exts2_calls = 0; g_exts2_groups = 0; }
+}
+
 // ======================================================================================================
 // GpuOps: the product implementation of the mapper's device operations
 // ======================================================================================================
@@ -243,6 +252,7 @@ struct GpuOpsCtx {
 	{
 		const size_t budget = (size_t)(c->arena_bytes * 0.6);
 		const int n = (int)reqs.size();
+		if (n > 0) ++g_exts2_calls;
 		for (int i0 = 0; i0 < n;) {
 			size_t need = 0, tot = 0, cap = 16;
 			int i1 = i0;
@@ -254,6 +264,7 @@ struct GpuOpsCtx {
 				need += b; tot += (size_t)r.ql + r.tl; cap += (size_t)r.ql + r.tl + 2;
 			}
 			const int m = i1 - i0;
+			++g_exts2_groups;
 			std::vector<wm_ksw_job_t> jobs(m);
 			std::vector<wm_ksw_result_t> res(m);
 			std::vector<uint8_t> seqs(tot + 1), junc;

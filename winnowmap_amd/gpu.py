@@ -309,6 +309,15 @@ def sdust_stats(reset=False):
     return {"window_calls": int(out[0]), "kernel_ms": float(out[1]), "jobs": int(out[2]), "host_jobs": int(out[3]), "list_high": int(out[4])}
 
 
+def exts2_stats(reset=False):
+    """wm_exts2_stats: splice mode's alignment calls of the mapper and the groups they were split into, process-wide since the last reset"""
+    out = np.zeros(2, np.uint64)
+    lib().wm_exts2_stats.argtypes = [C.c_void_p, C.c_int]
+    lib().wm_exts2_stats.restype = None
+    lib().wm_exts2_stats(out.ctypes.data, 1 if reset else 0)
+    return {"calls": int(out[0]), "groups": int(out[1])}
+
+
 def build_defines():
     """the kernel-variant defines the loaded library was compiled with (wm_build_defines)"""
     lib().wm_build_defines.restype = C.c_char_p
