@@ -120,6 +120,41 @@ typedef struct { int32_t max_zdrop, t0, t1, q0, q1; } wm_zd_t;
 int wm_ksw_batch_pos_zd(wm_ctx_t *ctx, const wm_ksw_score_t *sc, int n_jobs, const wm_ksw_pos_t *jobs,
                         wm_ksw_result_t *results, uint32_t *cigar_pool, size_t cigar_cap, size_t *cigar_used, wm_zd_t *zd);
 
+/* The scan of mm_update_extra (src/align.c:240-286) over FINAL CIGARs (after mm_fix_cigar, always in forward order), as a batch: dp_max (the best
+ * local score along the alignment), mlen, blen and the ambiguous bases this walk counts, plus the query / target lengths the CIGAR consumes — wm_extra_t of
+ * csrc/cigar_walk.h, whose wm_extra_walk is the specification. The scan is an associative fold (csrc/extra_kernel.h): a region's CIGAR is cut into tiles
+ * of columns that lanes, wavefronts and — for a long region — workgroups share. score: LITERAL values (mat[0], mat[1], mat[24] of ksw_gen_simple_mat; opt->q,
+ * opt->e), none of wm_ksw_score_t's conventions. cigars: n_ops BAM-encoded ops (len << 4 | op), job i owns [cig_off, cig_off + n_cigar); n_cigar == 0 gives zeros.
+ *   wm_extra_batch      operands as 0..4 codes inside seqs (q_off / t_off: first base of the query / target)
+ *   wm_extra_batch_pos  operands as positions in what the device holds, the rule of wm_ksw_pos_t without a step: query base i = index q_pos + i of the
+ *                       two-strand space of the (sub)read at qwin_off / qwin_len ([0, L) forward, [L, 2L) reverse complement, outside N), target base i =
+ *                       base t_pos + i of contig rid. Nothing but the CIGARs is shipped; the packed words are read as they are.
+ * WM_EINVAL, naming the job: a CIGAR that consumes more query or target than the operand holds (seqs_bytes, the resident reads, the contig) or ops beyond
+ * n_ops, and a job whose max(|match|, |mismatch|, |ambi|) * (M columns) + sum over its I / D ops of (q + e * len) exceeds WM_EXTRA_MAX_ABS (64-bit
+ * arithmetic): below it every value of the kernels' int32 arithmetic is exact. The reference has no such limit (its int32 s simply wraps). */
+#define WM_EXTRA_MAX_ABS (1 << 30)
+typedef struct { int32_t match, mismatch, ambi, q, e; } wm_extra_score_t;
+typedef struct { uint32_t q_off, t_off; uint32_t cig_off; int32_t n_cigar; } wm_extra_job_t;
+typedef struct { int64_t qwin_off; int32_t qwin_len, q_pos, rid, t_pos; uint32_t cig_off; int32_t n_cigar; } wm_extra_pos_t;
+typedef struct { int32_t dp_max, mlen, blen, n_ambi, qoff, toff; } wm_extra_res_t;
+int wm_extra_batch(wm_ctx_t *ctx, const wm_extra_score_t *score, int n_jobs, const wm_extra_job_t *jobs, const uint8_t *seqs, size_t seqs_bytes,
+                   const uint32_t *cigars, size_t n_ops, wm_extra_res_t *out);
+int wm_extra_batch_pos(wm_ctx_t *ctx, const wm_extra_score_t *score, int n_jobs, const wm_extra_pos_t *jobs, const uint32_t *cigars, size_t n_ops,
+                       wm_extra_res_t *out);
+/* Routing knob (process-wide; results never depend on it): a job of at least long_min_cols columns (M columns + one per 64 bases of an I / D op) is spread
+ * over one wavefront per tile of tile_cols columns plus a combine pass; a shorter one is walked tile by tile by ONE wavefront. tile_cols: a multiple of 64,
+ * at least 64 (anything else is ignored). < 0 = leave. Defaults 32768 / 512. wm_extra_tile_cols(): the current tile size. Tests force either class at tiny sizes. */
+void wm_extra_set_routing(int long_min_cols, int tile_cols);
+int wm_extra_tile_cols(void);
+/* The mapper's switch: on = 1, regions' final scans are deferred and go out as one batched wm_extra_batch_pos per read (just before the regions are
+ * filtered) instead of running on the host behind every region; 0 = the host walk; < 0 = what WM_EXTRA_DEV in the environment says (read when a mapping call
+ * starts). OFF by default. mm_fix_cigar stays on the host either way. Results do not depend on it. */
+void wm_set_extra_device(int on);
+int wm_extra_device_enabled(void);
+/* out6: regions deferred, regions walked on the device, regions walked on the host while the switch was on, batched device calls, alignment columns walked
+ * on the device (M columns + gap bases), microseconds the mapper spent inside those calls — process-wide since the last reset. */
+void wm_extra_stats(uint64_t *out6, int reset);
+
 /* diagnostics: per-phase cycle table of the stripe-pipelined wide-hull kernel; only in a library built with WM_KERNEL_DEFINES="WM_STRIPE_TIMING=1"
  * (WM_EINVAL otherwise). out16: cycles summed over wavefronts in scan / epoch set-up / cells / wait-left / bookkeeping / wait-right / publish, then rows,
  * epochs, total cycles, wavefronts. */

@@ -53,12 +53,12 @@ def _newer(target, sources):
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value", "-mllvm", "-disable-promote-alloca-to-vector"]
 
 
-UNITS = ("wm_rt", "wm_ksw", "wm_index", "wm_window", "wm_mapper")      # the translation units of libwmgpu.so (csrc/wm_rt.h says what each holds)
+UNITS = ("wm_rt", "wm_ksw", "wm_extra", "wm_index", "wm_window", "wm_mapper")      # the translation units of libwmgpu.so (csrc/wm_rt.h says what each holds)
 
 
 def build_gpu(force=False, verbose=False, out=None):
     """libwmgpu.so (or `out`: a variant library for A/B runs, selected with WM_LIBWMGPU=<path>; built here so that no GPU minute is spent compiling).
-    The five units are compiled side by side (objects under csrc/.obj/<library name>/, git-ignored) and linked into the one shared object."""
+    The units are compiled side by side (objects under csrc/.obj/<library name>/, git-ignored) and linked into the one shared object."""
     global LIB
     if out is not None:
         saved, LIB = LIB, out
@@ -189,6 +189,20 @@ def build_emu_sketchsteps():
     return out
 
 
+def build_emu_extra():
+    """tests/simt_emu/libwm_emu_extra.so: the fold of mm_update_extra's scan over final CIGARs (csrc/extra_kernel.h: prefix pass, both classes, byte and
+    position form) on the emulator (tests/simt_emu/emu_extra.cpp)."""
+    emu = os.path.join(ROOT, "tests", "simt_emu")
+    out = os.path.join(emu, "libwm_emu_extra.so")
+    srcs = [os.path.join(emu, f) for f in ("emu_extra.cpp", "simt.h")] + [os.path.join(CSRC, f) for f in ("extra_kernel.h", "reads2bit.h")] + \
+           [os.path.join(ROOT, "include", "wm_gpu.h")]
+    with _Lock(out):
+        if _newer(out, srcs):
+            _run_to(out, lambda o: ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
+                                    "-I" + emu, "-I" + CSRC, "-o", o, os.path.join(emu, "emu_extra.cpp")])
+    return out
+
+
 def build_emu_stripe(defines=()):
     """tests/simt_emu/libwm_emu_stripe[_<defines>].so: the stripe-pipelined ksw kernel alone on the emulator, with its event counters and the
     polling watchdog (tests/simt_emu/emu_stripe.cpp). ("WM_STRIPE_TEST_SLACK=...",) builds the variant whose bookkeeping margin is useless, so that
@@ -242,6 +256,7 @@ if __name__ == "__main__":
     build_emu_sdust()
     build_emu_evenk()
     build_emu_sketchsteps()
+    build_emu_extra()
     build_emu_stripe()
     build_emu_chain()
     build_harness()

@@ -159,6 +159,7 @@ struct AlnEnv {
 	const MapOpt *opt; const Index *idx; int qlen; const uint8_t *qseq0[2]; int8_t mat[25];
 	int64_t q_dev_off;      // where qcodes[0] lives in the resident read codes (-1: not resident), see KswReq
 	bool q_has_n;
+	bool defer_extra = false;   // the regions' final scans wait for one batched request per read (Scheduler::extra_deferred)
 };
 
 // one ksw request on query strand `rev`, strand coordinates [qs, qe), and reference [rs, re) of contig rid; `tb` = codes of the
@@ -498,22 +499,38 @@ void extra_walk_both(const uint8_t *qseq, const uint8_t *tseq, const uint32_t *c
 	memcpy(fast6, &a, sizeof(a)); memcpy(generic6, &b, sizeof(b));
 }
 
-static void update_extra(Reg &r, const uint8_t *qseq, const uint8_t *tseq, const int8_t *mat, int q, int e)
+void extra_walk_host(const uint8_t *qseq, const uint8_t *tseq, const uint32_t *cigar, int n_cigar, int match, int mismatch, int ambi, int q, int e, wm_extra_t *out)
+{
+#if defined(__SSE2__)
+	if (match > 0) { extra_walk_fast(qseq, tseq, cigar, n_cigar, match, mismatch, ambi, q, e, out); return; }
+#endif
+	wm_extra_walk(qseq, tseq, cigar, n_cigar, match, mismatch, ambi, q, e, out);
+}
+
+// mm_update_extra (src/align.c:240-286) in two halves: mm_fix_cigar, which runs where the region is finished, and the scan of the final CIGAR, whose four results
+// nothing reads before the regions of the read are filtered. With the switch on (wm_ops.h: extra_device_on) the scan waits — ExtraPend keeps what it will read — and
+// align_skeleton sends the scans of all regions of the read as ONE batched request (Scheduler::extra); with it off the scan runs here, as it always did.
+struct ExtraPend { bool on = false; const uint8_t *qp = 0, *tp = 0; int32_t q_pos = 0, rid = -1, t_pos = 0; };
+
+static void store_extra(Reg &r, const wm_extra_t &x)
+{
+	r.blen = x.blen; r.mlen = x.mlen; r.n_ambi += x.n_ambi; r.dp_max = x.dp_max;
+	const int32_t qoff = x.qoff, toff = x.toff; (void)qoff; (void)toff;
+	WM_INVARIANT(qoff == r.qe - r.qs && toff == r.re - r.rs);
+}
+
+// pend != 0: defer the scan. q_pos / rid / t_pos: where qseq[0] / tseq[0] sit in two-strand space / on the contig (the positions a device implementation reads)
+static void update_extra(Reg &r, const uint8_t *qseq, const uint8_t *tseq, const int8_t *mat, int q, int e, ExtraPend *pend = 0, int32_t q_pos = 0, int32_t rid = -1, int32_t t_pos = 0)
 {
 	WM_PROF("align.update_extra");   // mm_update_extra, src/align.c:240-286 (no =/X rewriting: MM_F_EQX is applied at output time if requested)
 	if (!r.has_p) return;
 	int qshift, tshift;
 	fix_cigar(r, qseq, tseq, &qshift, &tshift);
 	qseq += qshift, tseq += tshift;
+	if (pend) { pend->on = true; pend->qp = qseq; pend->tp = tseq; pend->q_pos = q_pos + qshift; pend->rid = rid; pend->t_pos = t_pos + tshift; return; }
 	wm_extra_t x;
-#if defined(__SSE2__)
-	if (mat[0] > 0) extra_walk_fast(qseq, tseq, r.cigar.data(), (int)r.cigar.size(), mat[0], mat[1], mat[24], q, e, &x);
-	else
-#endif
-	wm_extra_walk(qseq, tseq, r.cigar.data(), (int)r.cigar.size(), mat[0], mat[1], mat[24], q, e, &x);
-	r.blen = x.blen; r.mlen = x.mlen; r.n_ambi += x.n_ambi; r.dp_max = x.dp_max;
-	const int32_t qoff = x.qoff, toff = x.toff; (void)qoff; (void)toff;
-	WM_INVARIANT(qoff == r.qe - r.qs && toff == r.re - r.rs);
+	extra_walk_host(qseq, tseq, r.cigar.data(), (int)r.cigar.size(), mat[0], mat[1], mat[24], q, e, &x);
+	store_extra(r, x);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -531,6 +548,7 @@ struct RegAln {
 	std::vector<int> redo_code;
 	bool empty = false;
 	std::vector<uint8_t> tbuf;       // reference codes of [rs0, re0): every DP of the region and the final statistics read from here
+	ExtraPend xp;                    // the region's deferred final scan (reads tbuf: align_skeleton keeps it alive)
 	bool t_has_n = false;
 };
 
@@ -754,12 +772,14 @@ static void finish_reg(const AlnEnv &E, RegAln &A, m128 *a, const std::vector<Ks
 	else r.qs = qs1, r.qe = qe1;
 	if (r.has_p) {
 		WM_INVARIANT(rs1 >= A.rs0 && re1 <= A.re0);
-		update_extra(r, E.qseq0[r.rev] + qs1, A.tbuf.data() + (rs1 - A.rs0), E.mat, opt.q, opt.e);
+		const uint8_t *q0 = E.qseq0[r.rev] + qs1;
+		update_extra(r, q0, A.tbuf.data() + (rs1 - A.rs0), E.mat, opt.q, opt.e, E.defer_extra ? &A.xp : 0, (int32_t)(q0 - E.qseq0[0]), A.rid, rs1);
 	}
 }
 
 // mm_align1_inv (src/align.c:797-852): try to align the reverse strand between two pieces split by an inversion z-drop
-static bool align_inv(Scheduler &sch, const AlnEnv &E, const Reg &r1, const Reg &r2, Reg &r_inv)
+// xp / keep_t: the deferred final scan of the piece and the target codes it reads (AlnEnv::defer_extra)
+static bool align_inv(Scheduler &sch, const AlnEnv &E, const Reg &r1, const Reg &r2, Reg &r_inv, ExtraPend &xp, std::vector<uint8_t> &keep_t)
 {
 	const MapOpt &opt = *E.opt;
 	r_inv = Reg();
@@ -797,7 +817,9 @@ static bool align_inv(Scheduler &sch, const AlnEnv &E, const Reg &r1, const Reg 
 	else { r_inv.qe = r2.qs - q_off; r_inv.qs = r_inv.qe - (j.ez.max_q + 1); }
 	r_inv.rs = r1.re + t_off;
 	r_inv.re = r_inv.rs + j.ez.max_t + 1;
-	update_extra(r_inv, qstart, &tseq[t_off], E.mat, opt.q, opt.e);
+	// (qstart may lie up to 7 bases in front of its strand: in two-strand space the tail of the other strand, or the N padding in front of strand 0)
+	update_extra(r_inv, qstart, &tseq[t_off], E.mat, opt.q, opt.e, E.defer_extra ? &xp : 0, (int32_t)(qstart - E.qseq0[0]), r1.rid, r1.re + t_off);
+	if (xp.on) keep_t = std::move(tseq);                               // (a moved vector keeps its storage: xp.tp stays valid)
 	return true;
 }
 
@@ -805,6 +827,7 @@ void align_skeleton(Scheduler &sch, const MapOpt &opt, const Index &idx, int qle
 {
 	AlnEnv E;
 	E.opt = &opt; E.idx = &idx; E.qlen = qlen; E.q_dev_off = q_dev_off; E.q_has_n = false;
+	E.defer_extra = sch.extra_deferred();
 	// both strands in ONE buffer, reverse complement right behind the forward strand, exactly like the reference's
 	// qseq0 (src/align.c:871-877): mm_align1_inv may step a few bases in front of a strand (see align_inv)
 	// (three flat loops the compiler vectorises — a copy, a reversed complement, an OR-reduction — instead of one byte loop with two branches:
@@ -831,6 +854,10 @@ void align_skeleton(Scheduler &sch, const MapOpt &opt, const Index &idx, int qle
 	struct Node { Reg r; bool pending; };
 	std::list<Node> L;
 	for (Reg &r : regs) L.push_back(Node{ std::move(r), true });
+	// deferred final scans (the switch on): the region each belongs to — list nodes do not move —, what it reads, and the target codes kept alive for it
+	struct Deferred { Reg *r; ExtraPend p; };
+	std::vector<Deferred> deferred;
+	std::list<std::vector<uint8_t>> keep_t;
 	for (;;) {
 		std::vector<std::list<Node>::iterator> todo;
 		for (auto it = L.begin(); it != L.end(); ++it) if (it->pending) todo.push_back(it);
@@ -865,14 +892,31 @@ void align_skeleton(Scheduler &sch, const MapOpt &opt, const Index &idx, int qle
 			} else if (is_splice && A[k].r.has_p) A[k].r.trans_strand = (opt.flag & F_SPLICE_FOR) ? 1 : 2;
 			auto it = todo[k];
 			it->r = std::move(A[k].r); it->pending = false;
+			if (A[k].xp.on) { keep_t.push_back(std::move(A[k].tbuf)); deferred.push_back(Deferred{ &it->r, A[k].xp }); }
 			auto after = std::next(it);
 			// inversion rescue between this piece and its predecessor (src/align.c:906-911)
 			if (it != L.begin() && it->r.split_inv) {
-				Reg inv;
-				if (align_inv(sch, E, std::prev(it)->r, it->r, inv)) L.insert(after, Node{ std::move(inv), false });
+				Reg inv; ExtraPend ip; std::vector<uint8_t> inv_t;
+				if (align_inv(sch, E, std::prev(it)->r, it->r, inv, ip, inv_t)) {
+					auto at = L.insert(after, Node{ std::move(inv), false });
+					if (ip.on) { keep_t.push_back(std::move(inv_t)); deferred.push_back(Deferred{ &at->r, ip }); }
+				}
 			}
 			if (A[k].r2.cnt > 0) L.insert(after, Node{ std::move(A[k].r2), true });
 		}
+	}
+	if (!deferred.empty()) {          // nothing above reads blen, mlen, dp_max or n_ambi: one batched request for the whole read, just before filter_regs does
+		std::vector<ExtraReq> xr(deferred.size());
+		for (size_t i = 0; i < xr.size(); ++i) {
+			const Deferred &d = deferred[i];
+			ExtraReq &x = xr[i];
+			x.qp = d.p.qp; x.tp = d.p.tp; x.qwin_off = E.q_dev_off; x.qwin_len = qlen; x.q_pos = d.p.q_pos; x.rid = d.p.rid; x.t_pos = d.p.t_pos;
+			x.cigar = d.r->cigar.data(); x.n_cigar = (int)d.r->cigar.size();
+			x.sc.match = E.mat[0]; x.sc.mismatch = E.mat[1]; x.sc.ambi = E.mat[24]; x.sc.q = opt.q; x.sc.e = opt.e;
+		}
+		extra_stats().deferred += xr.size();
+		sch.extra(xr);
+		for (size_t i = 0; i < xr.size(); ++i) store_extra(*deferred[i].r, xr[i].out);
 	}
 	regs.clear();
 	for (Node &n : L) regs.push_back(std::move(n.r));

@@ -240,6 +240,7 @@ void map_batch(const Index &idx, const MapOpt &opt, DeviceOps *ops, const std::v
 	const long inflight_env = getenv("WM_INFLIGHT") ? atol(getenv("WM_INFLIGHT")) : 0;
 	const size_t window = std::max<size_t>(1, (size_t)(inflight_env > 0 ? inflight_env : 16384) / (size_t)T);
 	Hub hub(ops, sc, idx.w, idx.k);
+	hub.extra_dev = extra_device_on();          // (read when the mapping call starts: wm_set_extra_device / WM_EXTRA_DEV)
 	hub.n_workers = T;
 	hub.max_sw_mat = opt.max_sw_mat;
 	hub.splice = (opt.flag & F_SPLICE) != 0; hub.noncan = opt.noncan; hub.junc_bonus = opt.junc_bonus;
@@ -288,7 +289,7 @@ void map_batch(const Index &idx, const MapOpt &opt, DeviceOps *ops, const std::v
 		if (getenv("WM_TRACE")) { for (auto &e : hub.site_cpu) fprintf(stderr, "[site] %-28s %8.2f s CPU\n", e.first, e.second); }
 		stats->cpu_fiber += hub.cpu_fiber; stats->wall_idle += hub.wall_idle; stats->cpu_help += hub.cpu_help;
 		stats->wall_fiber += hub.wall_fiber; stats->wall_lock += hub.wall_lock; stats->wall_total += hub.wall_total;
-		for (int op = 0; op < OP_N; ++op) {           // (the heavy alignment queues are reported with the ksw operation, the fused window call in the first slot)
+		for (int op = 0; op < OP_N; ++op) {           // (the heavy alignment queues and the deferred final scans are reported with the ksw operation, the fused window call in the first slot)
 			const int o = op == OP_WINDOW || op == OP_WINDOW_BIG ? 0 : op >= OP_KSW_HEAVY ? OP_KSW : op;
 			stats->n_batches[o] += hub.n_batches[op]; stats->cpu_op[o] += hub.cpu_op[op]; stats->wall_op[o] += hub.wall_op[op];
 		}

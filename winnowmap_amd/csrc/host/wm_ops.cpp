@@ -1,4 +1,5 @@
-// wm_ops.cpp — DeviceOps::window_batch composed from the per-operation batches (see wm_ops.h).
+// wm_ops.cpp — DeviceOps::window_batch composed from the per-operation batches, the host form of DeviceOps::extra_batch and the switch + account of
+// the deferred final scans (see wm_ops.h).
 #include "wm_ops.h"
 #include "wm_sdust.h"
 
@@ -52,4 +53,47 @@ void DeviceOps::window_batch(int w, int k, std::vector<WindowReq*> &reqs)
 	}
 }
 
+// ---- the scan of mm_update_extra as a deferred, batched operation ----------------------------------------------------------------------------
+static std::atomic<int> g_extra_dev(-1);          // -1: the environment decides (WM_EXTRA_DEV), read whenever a mapping call starts
+bool extra_device_on()
+{
+	const int v = g_extra_dev.load(std::memory_order_relaxed);
+	if (v >= 0) return v != 0;
+	const char *e = getenv("WM_EXTRA_DEV");
+	return e && atoi(e) != 0;
+}
+ExtraStats &extra_stats() { static ExtraStats s; return s; }
+// WM_EXTRA_REPORT=1: the account on stderr when the library is unloaded (a front end that is not ours — the benchmark — has no other way to ask)
+static struct ExtraReport {
+	~ExtraReport()
+	{
+		ExtraStats &s = extra_stats();
+		if (!getenv("WM_EXTRA_REPORT") || !s.deferred.load()) return;
+		fprintf(stderr, "[wm] extra: %llu regions deferred, %llu walked on the device, %llu on the host, %llu batched calls, %llu columns, %llu us inside the calls\n",
+		        (unsigned long long)s.deferred.load(), (unsigned long long)s.on_device.load(), (unsigned long long)s.on_host.load(), (unsigned long long)s.calls.load(),
+		        (unsigned long long)s.cols.load(), (unsigned long long)s.us.load());
+	}
+} g_extra_report;
+
+void DeviceOps::extra_batch(const wm_extra_score_t &sc, std::vector<ExtraReq*> &reqs)
+{
+	WM_SITE("extra.host_walk");
+	parallel_for(1, reqs.size(), [&](size_t i) {
+		ExtraReq &r = *reqs[i];
+		extra_walk_host(r.qp, r.tp, r.cigar, r.n_cigar, sc.match, sc.mismatch, sc.ambi, sc.q, sc.e, &r.out);
+	});
+	extra_stats().on_host += reqs.size();
+}
+
 } // namespace wm
+
+extern "C" {
+void wm_set_extra_device(int on) { wm::g_extra_dev = on < 0 ? -1 : on ? 1 : 0; }
+int wm_extra_device_enabled(void) { return wm::extra_device_on() ? 1 : 0; }
+void wm_extra_stats(uint64_t *out6, int reset)
+{
+	wm::ExtraStats &s = wm::extra_stats();
+	std::atomic<uint64_t> *f[6] = { &s.deferred, &s.on_device, &s.on_host, &s.calls, &s.cols, &s.us };
+	for (int i = 0; i < 6; ++i) { if (out6) out6[i] = f[i]->load(); if (reset) f[i]->store(0); }
+}
+}

@@ -5,6 +5,7 @@
 #pragma once
 #include "wm_core.h"
 #include "../cigar_walk.h"
+#include <atomic>
 
 namespace wm {
 
@@ -82,6 +83,26 @@ struct KswReq {                    // ksw_extd2_sse (src/ksw2.h:60)
 	void copy_target(uint8_t *dst) const { for (int i = 0; i < tl; ++i) dst[i] = tp[(ptrdiff_t)i * step]; }
 };
 
+struct ExtraReq {                  // the scan of mm_update_extra (src/align.c:240-286) over a region's FINAL CIGAR (after mm_fix_cigar, forward order)
+	// host views of both operands from the alignment's first base on, readable 16 bytes beyond the aligned stretch; valid while the request is pending
+	const uint8_t *qp = 0, *tp = 0;
+	// the same operands as positions in resident data, the rule of KswReq without a step: two-strand index q_pos of the (sub)read at qwin_off / qwin_len
+	// (mm_align1_inv's region may start a few bases in front of its strand: the tail of the other strand, or N padding), base t_pos of contig rid
+	int64_t qwin_off = -1; int32_t qwin_len = 0, q_pos = 0, rid = -1, t_pos = 0;
+	const uint32_t *cigar = 0; int n_cigar = 0;            // the region's CIGAR (stays where it is until the request is served)
+	wm_extra_score_t sc = { 0, 0, 0, 0, 0 };               // mat[0], mat[1], mat[24], opt->q, opt->e: one value per mapping call
+	wm_extra_t out = { 0, 0, 0, 0, 0, 0 };                 // out
+	bool resident() const { return qwin_off >= 0 && rid >= 0; }
+};
+// wm_extra_walk (csrc/cigar_walk.h), 16 bases per step where the build has SSE2 and match > 0 (host/wm_align.cpp)
+void extra_walk_host(const uint8_t *qseq, const uint8_t *tseq, const uint32_t *cigar, int n_cigar, int match, int mismatch, int ambi, int q, int e, wm_extra_t *out);
+
+// The mapper's switch for that scan (wm_set_extra_device / WM_EXTRA_DEV, include/wm_gpu.h; off by default) and its process-wide account (wm_extra_stats). They live
+// with the host mapper, so the test harness has them too.
+bool extra_device_on();
+struct ExtraStats { std::atomic<uint64_t> deferred{0}, on_device{0}, on_host{0}, calls{0}, cols{0}, us{0}; };
+ExtraStats &extra_stats();
+
 // The batch calls are synchronous (they return when the results are in the requests) and must be callable from several threads at
 // once: the hub (wm_fiber.h) keeps up to max_inflight() of them running concurrently.
 struct DeviceOps {
@@ -102,6 +123,9 @@ struct DeviceOps {
 	// splice mode: the same requests through ksw_exts2_sse (src/align.c:326-327) — no band, no end bonus, sc.q2 = the price of an intron;
 	// KswReq::flag carries the KSW_EZ_SPLICE_* bits. No junction annotation (mm_idx_bed_junc: the BED reader is outside the path).
 	virtual void exts2_batch(const wm_ksw_score_t &sc, int noncan, int junc_bonus, std::vector<KswReq*> &reqs) = 0;
+	// the deferred final scans of a mapping call's regions (the switch above). The default walks them on the host (wm_extra_walk / its SSE form) — checker-backed
+	// implementations need nothing; the product's GpuOps overrides it with wm_extra_batch_pos when every request is resident.
+	virtual void extra_batch(const wm_extra_score_t &sc, std::vector<ExtraReq*> &reqs);
 	// the whole window in one call. The default composes it from the three operations above (checker-backed implementations in the
 	// test-suite); the product's GpuOps overrides it with the HBM-resident wm_window_batch.
 	virtual void window_batch(int w, int k, std::vector<WindowReq*> &reqs);

@@ -247,6 +247,38 @@ struct GpuOpsCtx {
 		});
 		t_pack += t1 - t0; t_unpack += now_ms() - t2; t_prep += c->t_prep; t_run += c->t_run; t_fetch += c->t_fetch;
 	}
+	// the deferred final scans of regions (mm_update_extra's walk, src/align.c:240-286) through wm_extra_batch_pos: operands as positions in the resident reads and
+	// the uploaded reference, nothing but the CIGARs is shipped. Returns false — nothing done — unless every request is resident (the caller then walks on the host).
+	bool extra_batch(const wm_extra_score_t &sc, std::vector<wm::ExtraReq*> &reqs)
+	{
+		const int n = (int)reqs.size();
+		if (!resident) return false;
+		for (int i = 0; i < n; ++i) if (!reqs[i]->resident()) return false;
+		const double t0 = now_ms();
+		std::vector<wm_extra_pos_t> jobs(n);
+		size_t tot = 0;
+		for (int i = 0; i < n; ++i) {
+			const wm::ExtraReq &r = *reqs[i];
+			wm_extra_pos_t &j = jobs[i];
+			j.qwin_off = r.qwin_off; j.qwin_len = r.qwin_len; j.q_pos = r.q_pos; j.rid = r.rid; j.t_pos = r.t_pos; j.cig_off = (uint32_t)tot; j.n_cigar = r.n_cigar;
+			tot += (size_t)r.n_cigar;
+		}
+		if (tot >= ((size_t)1 << 31)) { error = "extra batch exceeds 2^31 CIGAR ops"; return true; }
+		UBuf<uint32_t> cig(tot + 1, c);
+		WM_SITE("extra.cigars");
+		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) { if (reqs[i]->n_cigar) memcpy(cig.data() + jobs[i].cig_off, reqs[i]->cigar, (size_t)reqs[i]->n_cigar * 4); });
+		std::vector<wm_extra_res_t> res(n);
+		if (wm_extra_batch_pos(c, &sc, n, jobs.data(), cig.data(), tot, res.data())) { fail("extra"); return true; }
+		uint64_t cols = 0;
+		for (int i = 0; i < n; ++i) {
+			static_assert(sizeof(wm_extra_res_t) == sizeof(wm_extra_t), "wm_extra_res_t is wm_extra_t");
+			memcpy(&reqs[i]->out, &res[i], sizeof(wm_extra_t));
+			cols += (uint64_t)(res[i].blen + res[i].n_ambi);
+		}
+		wm::ExtraStats &st = wm::extra_stats();
+		st.on_device += (uint64_t)n; ++st.calls; st.cols += cols; st.us += (uint64_t)((now_ms() - t0) * 1e3);
+		return true;
+	}
 	// splice mode (src/align.c:326-327): the requests through wm_ksw_exts2_batch, in groups whose unbanded traceback matrices fit the arena
 	void exts2_batch(const wm_ksw_score_t &sc, int noncan, int junc_bonus, std::vector<wm::KswReq*> &reqs)
 	{
@@ -416,6 +448,12 @@ struct GpuOps {                          // the device contexts of a mapper, sha
 	void chain_batch(wm::ErrorSink &e, std::vector<wm::ChainReq*> &reqs) { with(e, [&](GpuOpsCtx &x) { run_split(x, reqs, [&](std::vector<wm::ChainReq*> &part) { x.chain_batch(part); }); }); }
 	void ksw_batch(wm::ErrorSink &e, const wm_ksw_score_t &sc, std::vector<wm::KswReq*> &reqs) { with(e, [&](GpuOpsCtx &x) { x.ksw_batch(sc, reqs); }); }
 	void exts2_batch(wm::ErrorSink &e, const wm_ksw_score_t &sc, int noncan, int junc_bonus, std::vector<wm::KswReq*> &reqs) { with(e, [&](GpuOpsCtx &x) { x.exts2_batch(sc, noncan, junc_bonus, reqs); }); }
+	// *served = false: some request is not resident (or the mapping call has failed already): nothing was done
+	void extra_batch(wm::ErrorSink &e, const wm_extra_score_t &sc, std::vector<wm::ExtraReq*> &reqs, bool *served)
+	{
+		*served = false;
+		with(e, [&](GpuOpsCtx &x) { bool all = true; run_split(x, reqs, [&](std::vector<wm::ExtraReq*> &part) { all = x.extra_batch(sc, part) && all; }); *served = all; });
+	}
 	// collect_seed_hits takes one (max_occ, flag) per call: the mapper's requests of one mapping call all share them
 	void window_batch(wm::ErrorSink &e, std::vector<wm::WindowReq*> &reqs) { with(e, [&](GpuOpsCtx &x) { run_split(x, reqs, [&](std::vector<wm::WindowReq*> &part) { x.window_batch(part); }); }); }
 };
@@ -442,6 +480,12 @@ struct CallOps : wm::DeviceOps {
 	void ksw_batch(const wm_ksw_score_t &sc, std::vector<wm::KswReq*> &reqs) override { g.ksw_batch(err, sc, reqs); }
 	void exts2_batch(const wm_ksw_score_t &sc, int noncan, int junc_bonus, std::vector<wm::KswReq*> &reqs) override { g.exts2_batch(err, sc, noncan, junc_bonus, reqs); }
 	void window_batch(int, int, std::vector<wm::WindowReq*> &reqs) override { g.window_batch(err, reqs); }
+	void extra_batch(const wm_extra_score_t &sc, std::vector<wm::ExtraReq*> &reqs) override
+	{
+		bool served = false;
+		g.extra_batch(err, sc, reqs, &served);
+		if (!served) wm::DeviceOps::extra_batch(sc, reqs);          // a request that is not resident: the host walk (counted by wm_extra_stats)
+	}
 };
 
 struct wm_mapper_s {

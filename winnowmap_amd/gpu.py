@@ -142,6 +142,31 @@ class Context:
         _chk(lib().wm_ksw_batch_pos_zd(self._h, C.byref(score), len(jobs), jobs.ctypes.data, res.ctypes.data, pool.ctypes.data, cap, C.byref(used), zd.ctypes.data))
         return res, pool[:used.value], zd
 
+    # ---- the scan of mm_update_extra over final CIGARs ----------------------------------------------
+    def extra_batch(self, score, jobs, seqs, cigars):
+        """wm_extra_batch: score = (match, mismatch, ambi, q, e) as literal values; jobs: structured array EXTRA_JOB_DTYPE (operands as 0..4 codes inside
+        seqs); cigars: uint32 BAM ops. Returns int32 [n, 6] = dp_max, mlen, blen, n_ambi, qoff, toff per job."""
+        jobs = np.ascontiguousarray(jobs, EXTRA_JOB_DTYPE)
+        seqs = np.ascontiguousarray(seqs, np.uint8)
+        cigars = np.ascontiguousarray(cigars, np.uint32)
+        sc = np.array(score, np.int32)
+        assert EXTRA_JOB_DTYPE.itemsize == 16 and sc.shape == (5,)
+        out = np.zeros((len(jobs), 6), np.int32)
+        lib().wm_extra_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        _chk(lib().wm_extra_batch(self._h, sc.ctypes.data, len(jobs), jobs.ctypes.data, seqs.ctypes.data, seqs.nbytes, cigars.ctypes.data, len(cigars), out.ctypes.data))
+        return out
+
+    def extra_batch_pos(self, score, jobs, cigars):
+        """wm_extra_batch_pos: jobs: structured array EXTRA_POS_DTYPE (operands as positions in the resident reads, two-strand space, and the uploaded reference)"""
+        jobs = np.ascontiguousarray(jobs, EXTRA_POS_DTYPE)
+        cigars = np.ascontiguousarray(cigars, np.uint32)
+        sc = np.array(score, np.int32)
+        assert EXTRA_POS_DTYPE.itemsize == 32 and sc.shape == (5,)
+        out = np.zeros((len(jobs), 6), np.int32)
+        lib().wm_extra_batch_pos.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        _chk(lib().wm_extra_batch_pos(self._h, sc.ctypes.data, len(jobs), jobs.ctypes.data, cigars.ctypes.data, len(cigars), out.ctypes.data))
+        return out
+
     def seed_batch_keyed(self, mini, mini_off, n_mini, qlen, keys, max_occ, flag, out_cap):
         """wm_seed_batch_keyed: collect_seed_hits with skip_seed's name comparison (src/map.c:132-154). mini: uint64 [n_total, 2]; keys: uint32 [n, 2]
         from Index.query_keys (None = wm_seed_batch: MM_F_NO_DIAG / MM_F_NO_DUAL are ignored). Returns (anchors uint64 [out_cap, 2], out_off, n_anchors, rep_len)."""
@@ -252,6 +277,47 @@ class KswDevBatch:
         if self._h:
             lib().wm_ksw_dev_free(self.ctx._h, self._h)
             self._h = None
+
+
+EXTRA_JOB_DTYPE = np.dtype([("q_off", np.uint32), ("t_off", np.uint32), ("cig_off", np.uint32), ("n_cigar", np.int32)])                       # wm_extra_job_t
+EXTRA_POS_DTYPE = np.dtype([("qwin_off", np.int64), ("qwin_len", np.int32), ("q_pos", np.int32), ("rid", np.int32), ("t_pos", np.int32),
+                            ("cig_off", np.uint32), ("n_cigar", np.int32)])                                                                      # wm_extra_pos_t
+EXTRA_MAX_ABS = 1 << 30                                                                                                                          # WM_EXTRA_MAX_ABS
+EXTRA_STAT_NAMES = ("deferred", "on_device", "on_host", "calls", "columns", "device_us")
+
+
+def set_extra_routing(long_min_cols=-1, tile_cols=-1):
+    """wm_extra_set_routing: from how many columns a final CIGAR is spread over one wavefront per tile, and the tile size (results never depend on it)"""
+    lib().wm_extra_set_routing.argtypes = [C.c_int, C.c_int]
+    lib().wm_extra_set_routing.restype = None
+    lib().wm_extra_set_routing(long_min_cols, tile_cols)
+
+
+def extra_tile_cols():
+    lib().wm_extra_tile_cols.restype = C.c_int
+    return int(lib().wm_extra_tile_cols())
+
+
+def set_extra_device(on):
+    """wm_set_extra_device: the mapper defers its regions' final scans (mm_update_extra's walk) to one batched device call per read (off by default;
+    on < 0: back to what WM_EXTRA_DEV in the environment says). Read when a mapping call starts; results never depend on it."""
+    lib().wm_set_extra_device.argtypes = [C.c_int]
+    lib().wm_set_extra_device.restype = None
+    lib().wm_set_extra_device(int(on))
+
+
+def extra_device_enabled():
+    lib().wm_extra_device_enabled.restype = C.c_int
+    return bool(lib().wm_extra_device_enabled())
+
+
+def extra_stats(reset=False):
+    """wm_extra_stats: regions deferred / walked on the device / walked on the host while the switch was on, batched device calls, columns, microseconds"""
+    out = np.zeros(6, np.uint64)
+    lib().wm_extra_stats.argtypes = [C.c_void_p, C.c_int]
+    lib().wm_extra_stats.restype = None
+    lib().wm_extra_stats(out.ctypes.data, 1 if reset else 0)
+    return dict(zip(EXTRA_STAT_NAMES, (int(x) for x in out)))
 
 
 def set_ksw_routing(on=-1, rows4=-1, rows8=-1):
