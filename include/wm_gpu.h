@@ -141,6 +141,20 @@ int wm_extra_batch(wm_ctx_t *ctx, const wm_extra_score_t *score, int n_jobs, con
                    const uint32_t *cigars, size_t n_ops, wm_extra_res_t *out);
 int wm_extra_batch_pos(wm_ctx_t *ctx, const wm_extra_score_t *score, int n_jobs, const wm_extra_pos_t *jobs, const uint32_t *cigars, size_t n_ops,
                        wm_extra_res_t *out);
+/* mm_fix_cigar (src/align.c:91-167) on the device, fused with the scan above (src/align.c:240-286 as a whole): cigars holds each region's STITCHED CIGAR; the call
+ * left-aligns every indel between two M ops, merges runs like 5I6D7I, squeezes and merges (only where the reference does) and drops ONE leading I / D, exactly as
+ * wm_fix_cigar of csrc/cigar_fix.h does (the specification; kernel: csrc/fix_kernel.h, one wavefront per job). cigars_out (n_ops words): job i's fixed CIGAR at its own
+ * cig_off, fix_out[i].n_cigar ops (never more than it had); qshift / tshift = the length of the leading I / D that went (the caller applies  rev ? qe -= qshift :
+ * qs += qshift,  rs += tshift); changed = the CIGAR or its count differs. score and extra_out both NULL: the fix alone. Otherwise extra_out[i] is what
+ * wm_extra_batch[_pos] gives for the fixed CIGAR with the operands advanced by qshift / tshift (the query in two-strand space). Jobs are validated, sized and
+ * routed from the RAW CIGAR — mm_fix_cigar never raises the WM_EXTRA_MAX_ABS bound or the column count — so every refusal of wm_extra_batch[_pos] applies as it
+ * stands. Also WM_EINVAL, naming the job: a zero-length op of code >= 3 (the reference indexes s[op] out of bounds there, :132) and lengths that add up to 2^31 or
+ * more. Op codes above 3 with a length are inert, as in the reference. Results do not depend on wm_extra_set_routing. */
+typedef struct { int32_t n_cigar, qshift, tshift, changed; } wm_fix_res_t;
+int wm_fix_extra_batch(wm_ctx_t *ctx, const wm_extra_score_t *score, int n_jobs, const wm_extra_job_t *jobs, const uint8_t *seqs, size_t seqs_bytes,
+                       const uint32_t *cigars, size_t n_ops, uint32_t *cigars_out, wm_fix_res_t *fix_out, wm_extra_res_t *extra_out);
+int wm_fix_extra_batch_pos(wm_ctx_t *ctx, const wm_extra_score_t *score, int n_jobs, const wm_extra_pos_t *jobs, const uint32_t *cigars, size_t n_ops,
+                           uint32_t *cigars_out, wm_fix_res_t *fix_out, wm_extra_res_t *extra_out);
 /* Routing knob (process-wide; results never depend on it): a job of at least long_min_cols columns (M columns + one per 64 bases of an I / D op) is spread
  * over one wavefront per tile of tile_cols columns plus a combine pass; a shorter one is walked tile by tile by ONE wavefront. tile_cols: a multiple of 64,
  * at least 64 (anything else is ignored). < 0 = leave. Defaults 32768 / 512. wm_extra_tile_cols(): the current tile size. Tests force either class at tiny sizes. */
@@ -154,6 +168,18 @@ int wm_extra_device_enabled(void);
 /* out6: regions deferred, regions walked on the device, regions walked on the host while the switch was on, batched device calls, alignment columns walked
  * on the device (M columns + gap bases), microseconds the mapper spent inside those calls — process-wide since the last reset. */
 void wm_extra_stats(uint64_t *out6, int reset);
+/* The mapper's switch for BOTH halves of mm_update_extra: on = 1, a region keeps its stitched CIGAR where it is finished, and mm_fix_cigar + the scan go out as one
+ * batched wm_fix_extra_batch_pos per read; a region that mm_align1_inv is about to read (src/align.c:906-911 reads qs / qe / rs / re, which mm_fix_cigar may move) gets
+ * the host fix there and then and only its scan is deferred. 0 = off; < 0 = what WM_FIX_DEV in the environment says (read when a mapping call starts). OFF by default;
+ * with it off nothing changes, whatever wm_set_extra_device says. Results do not depend on it. */
+void wm_set_fix_device(int on);
+int wm_fix_device_enabled(void);
+/* out7: regions whose fix was deferred, fixed on the device, fixed on the host by the batched request while the switch was on, fixed on the host early because an
+ * inversion test read them, batched device calls, microseconds the mapper spent inside those calls, alignment columns those calls walked (M columns + gap bases; they
+ * are NOT added to wm_extra_stats) — process-wide since the last reset. A request the device call refuses for WM_EXTRA_MAX_ABS or for its summed lengths fails the
+ * mapping call, as it does for wm_extra_batch_pos under wm_set_extra_device; only a request that is not resident, or holds a zero-length op of code >= 3, falls through
+ * to the host form. */
+void wm_fix_stats(uint64_t *out7, int reset);
 
 /* diagnostics: per-phase cycle table of the stripe-pipelined wide-hull kernel; only in a library built with WM_KERNEL_DEFINES="WM_STRIPE_TIMING=1"
  * (WM_EINVAL otherwise). out16: cycles summed over wavefronts in scan / epoch set-up / cells / wait-left / bookkeeping / wait-right / publish, then rows,

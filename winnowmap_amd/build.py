@@ -203,6 +203,35 @@ def build_emu_extra():
     return out
 
 
+def build_emu_fix():
+    """tests/simt_emu/libwm_emu_fix.so: mm_fix_cigar on the emulator (csrc/fix_kernel.h), alone and fused with the scan of extra_kernel.h, byte and position
+    form, beside the specification itself (csrc/cigar_fix.h) (tests/simt_emu/emu_fix.cpp)."""
+    emu = os.path.join(ROOT, "tests", "simt_emu")
+    out = os.path.join(emu, "libwm_emu_fix.so")
+    srcs = [os.path.join(emu, f) for f in ("emu_fix.cpp", "simt.h")] + \
+           [os.path.join(CSRC, f) for f in ("fix_kernel.h", "cigar_fix.h", "extra_kernel.h", "reads2bit.h")] + [os.path.join(ROOT, "include", "wm_gpu.h")]
+    with _Lock(out):
+        if _newer(out, srcs):
+            _run_to(out, lambda o: ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
+                                    "-I" + emu, "-I" + CSRC, "-o", o, os.path.join(emu, "emu_fix.cpp")])
+    return out
+
+
+def build_emu_fix_main(sanitize=True):
+    """tests/simt_emu/emu_fix_main[_san]: emu_fix.cpp with a main of its own (emu_fix_main.cpp) that replays the cases `python tests/fixcases.py dump FILE` wrote —
+    the stand-alone program for -fsanitize=address,undefined runs of the kernels' index arithmetic on the CPU."""
+    emu = os.path.join(ROOT, "tests", "simt_emu")
+    out = os.path.join(emu, "emu_fix_main_san" if sanitize else "emu_fix_main")
+    srcs = [os.path.join(emu, f) for f in ("emu_fix_main.cpp", "emu_fix.cpp", "simt.h")] + \
+           [os.path.join(CSRC, f) for f in ("fix_kernel.h", "cigar_fix.h", "extra_kernel.h", "reads2bit.h")] + [os.path.join(ROOT, "include", "wm_gpu.h")]
+    with _Lock(out):
+        if _newer(out, srcs):
+            _run_to(out, lambda o: ["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas"] +
+                                   (["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"] if sanitize else []) +
+                                   ["-I" + emu, "-I" + CSRC, "-o", o, os.path.join(emu, "emu_fix_main.cpp"), os.path.join(emu, "emu_fix.cpp")])
+    return out
+
+
 def build_emu_stripe(defines=()):
     """tests/simt_emu/libwm_emu_stripe[_<defines>].so: the stripe-pipelined ksw kernel alone on the emulator, with its event counters and the
     polling watchdog (tests/simt_emu/emu_stripe.cpp). ("WM_STRIPE_TEST_SLACK=...",) builds the variant whose bookkeeping margin is useless, so that
@@ -257,6 +286,7 @@ if __name__ == "__main__":
     build_emu_evenk()
     build_emu_sketchsteps()
     build_emu_extra()
+    build_emu_fix()
     build_emu_stripe()
     build_emu_chain()
     build_harness()

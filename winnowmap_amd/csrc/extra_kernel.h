@@ -35,15 +35,18 @@
 typedef struct { long long q_base, t_base; uint32_t cig_off, pre_off; int32_t n_cigar, q_pos, q_len, tile0; } wm_extra_djob_t;
 
 // what the host needs to know of a job before it goes out (64-bit): columns, bases consumed, and the bound of the limit above
-typedef struct { int64_t cols, qlen, tlen, abs_sum; } wm_extra_measure_t;
+// (for mm_fix_cigar in front of the scan, fix_kernel.h: total = all lengths added up; bad_zero = the first op of length 0 and code >= 3, or -1)
+typedef struct { int64_t cols, qlen, tlen, abs_sum, total; int32_t bad_zero; } wm_extra_measure_t;
 static inline wm_extra_measure_t wm_extra_measure(const uint32_t *cig, int n, const wm_extra_score_t *sc)
 {
-	wm_extra_measure_t r = { 0, 0, 0, 0 };
+	wm_extra_measure_t r = { 0, 0, 0, 0, 0, -1 };
 	int64_t mx = sc->match < 0 ? -(int64_t)sc->match : sc->match, m_cols = 0;
 	if (mx < (sc->mismatch < 0 ? -(int64_t)sc->mismatch : sc->mismatch)) mx = sc->mismatch < 0 ? -(int64_t)sc->mismatch : sc->mismatch;
 	if (mx < (sc->ambi < 0 ? -(int64_t)sc->ambi : sc->ambi)) mx = sc->ambi < 0 ? -(int64_t)sc->ambi : sc->ambi;
 	for (int k = 0; k < n; ++k) {
 		const int64_t op = cig[k] & 0xf, len = cig[k] >> 4;
+		r.total += len;
+		if (len == 0 && op >= 3 && r.bad_zero < 0) r.bad_zero = k;
 		if (op == 0) { m_cols += len; r.qlen += len; r.tlen += len; }
 		else if (op == 1 || op == 2) {
 			const int64_t g = (int64_t)sc->q + (int64_t)sc->e * len;

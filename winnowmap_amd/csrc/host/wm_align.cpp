@@ -1,6 +1,7 @@
 // wm_align.cpp — see wm_align.h.
 #include "wm_align.h"
 #include "../cigar_walk.h"
+#include "../cigar_fix.h"
 #include <math.h>
 #include <algorithm>
 #include <list>
@@ -159,6 +160,7 @@ struct AlnEnv {
 	const MapOpt *opt; const Index *idx; int qlen; const uint8_t *qseq0[2]; int8_t mat[25];
 	int64_t q_dev_off;      // where qcodes[0] lives in the resident read codes (-1: not resident), see KswReq
 	bool q_has_n;
+	bool defer_fix = false;     // ... and their mm_fix_cigar with them (Scheduler::fix_deferred)
 	bool defer_extra = false;   // the regions' final scans wait for one batched request per read (Scheduler::extra_deferred)
 };
 
@@ -382,60 +384,15 @@ static int test_zdrop(const MapOpt &opt, const uint8_t *qseq, const uint8_t *tse
 }
 
 static void fix_cigar(Reg &r, const uint8_t *qseq, const uint8_t *tseq, int *qshift, int *tshift)
-{   // mm_fix_cigar, src/align.c:91-167
-	std::vector<uint32_t> &cg = r.cigar;
-	int32_t toff = 0, qoff = 0, to_shrink = 0;
-	*qshift = *tshift = 0;
-	if (cg.size() <= 1) return;
-	for (uint32_t k = 0; k < cg.size(); ++k) {                         // left-align indels
-		const uint32_t op = cg[k] & 0xf, len = cg[k] >> 4;
-		if (len == 0) to_shrink = 1;
-		if (op == 0) toff += len, qoff += len;
-		else if (op == 1 || op == 2) {
-			if (k > 0 && k < cg.size() - 1 && (cg[k - 1] & 0xf) == 0 && (cg[k + 1] & 0xf) == 0) {
-				int l;
-				const int prev_len = cg[k - 1] >> 4;
-				if (op == 1) { for (l = 0; l < prev_len; ++l) if (qseq[qoff - 1 - l] != qseq[qoff + len - 1 - l]) break; }
-				else { for (l = 0; l < prev_len; ++l) if (tseq[toff - 1 - l] != tseq[toff + len - 1 - l]) break; }
-				if (l > 0) cg[k - 1] -= l << 4, cg[k + 1] += l << 4, qoff -= l, toff -= l;
-				if (l == prev_len) to_shrink = 1;
-			}
-			if (op == 1) qoff += len; else toff += len;
-		} else if (op == 3) toff += len;
-	}
+{   // mm_fix_cigar, src/align.c:91-167: the shared loop of cigar_fix.h, then the region's coordinates
+	int n = (int)r.cigar.size();
+	int32_t qoff = 0, toff = 0;
+	if (n <= 1) { *qshift = *tshift = 0; return; }
+	wm_fix_cigar(r.cigar.data(), &n, qseq, tseq, qshift, tshift, &qoff, &toff);
 	WM_INVARIANT(qoff == r.qe - r.qs && toff == r.re - r.rs);
-	for (uint32_t k = 0; k + 2 < cg.size(); ++k) {                     // 5I6D7I → one I and one D
-		if ((cg[k] & 0xf) > 0 && (cg[k] & 0xf) + (cg[k + 1] & 0xf) == 3) {
-			uint32_t l, s[3] = {0, 0, 0};
-			for (l = k; l < cg.size(); ++l) {
-				const uint32_t op = cg[l] & 0xf;
-				if (op == 1 || op == 2 || cg[l] >> 4 == 0) s[op] += cg[l] >> 4;
-				else break;
-			}
-			if (s[1] > 0 && s[2] > 0 && l - k > 2) {
-				cg[k] = s[1] << 4 | 1; cg[k + 1] = s[2] << 4 | 2;
-				for (k += 2; k < l; ++k) cg[k] &= 0xf;
-				to_shrink = 1;
-			}
-			k = l;
-		}
-	}
-	if (to_shrink) {
-		size_t l = 0;
-		for (size_t k = 0; k < cg.size(); ++k) if (cg[k] >> 4 != 0) cg[l++] = cg[k];
-		cg.resize(l);
-		l = 0;
-		for (size_t k = 0; k < cg.size(); ++k)
-			if (k == cg.size() - 1 || (cg[k] & 0xf) != (cg[k + 1] & 0xf)) cg[l++] = cg[k];
-			else cg[k + 1] += cg[k] >> 4 << 4;
-		cg.resize(l);
-	}
-	if ((cg[0] & 0xf) == 1 || (cg[0] & 0xf) == 2) {                    // no leading I/D
-		const int32_t l = cg[0] >> 4;
-		if ((cg[0] & 0xf) == 1) { if (r.rev) r.qe -= l; else r.qs += l; *qshift = l; }
-		else r.rs += l, *tshift = l;
-		cg.erase(cg.begin());
-	}
+	r.cigar.resize((size_t)n);
+	if (r.rev) r.qe -= *qshift; else r.qs += *qshift;
+	r.rs += *tshift;
 }
 
 // wm_extra_walk (cigar_walk.h) with the match stretches compared 16 bases per step. An ONT alignment alternates M runs of a dozen bases with short
@@ -510,7 +467,9 @@ void extra_walk_host(const uint8_t *qseq, const uint8_t *tseq, const uint32_t *c
 // mm_update_extra (src/align.c:240-286) in two halves: mm_fix_cigar, which runs where the region is finished, and the scan of the final CIGAR, whose four results
 // nothing reads before the regions of the read are filtered. With the switch on (wm_ops.h: extra_device_on) the scan waits — ExtraPend keeps what it will read — and
 // align_skeleton sends the scans of all regions of the read as ONE batched request (Scheduler::extra); with it off the scan runs here, as it always did.
-struct ExtraPend { bool on = false; const uint8_t *qp = 0, *tp = 0; int32_t q_pos = 0, rid = -1, t_pos = 0; };
+// With the other switch on (fix_device_on) mm_fix_cigar waits as well: fix = true, the region keeps its STITCHED CIGAR and ExtraPend the operands of that — until
+// the batched request returns the fixed CIGAR and both shifts, or until an inversion test needs the region's coordinates (align_skeleton: fix_now).
+struct ExtraPend { bool on = false, fix = false; const uint8_t *qp = 0, *tp = 0; int32_t q_pos = 0, rid = -1, t_pos = 0; };
 
 static void store_extra(Reg &r, const wm_extra_t &x)
 {
@@ -520,10 +479,16 @@ static void store_extra(Reg &r, const wm_extra_t &x)
 }
 
 // pend != 0: defer the scan. q_pos / rid / t_pos: where qseq[0] / tseq[0] sit in two-strand space / on the contig (the positions a device implementation reads)
-static void update_extra(Reg &r, const uint8_t *qseq, const uint8_t *tseq, const int8_t *mat, int q, int e, ExtraPend *pend = 0, int32_t q_pos = 0, int32_t rid = -1, int32_t t_pos = 0)
+// defer_fix: mm_fix_cigar waits too
+static void update_extra(Reg &r, const uint8_t *qseq, const uint8_t *tseq, const int8_t *mat, int q, int e, ExtraPend *pend = 0, int32_t q_pos = 0, int32_t rid = -1, int32_t t_pos = 0,
+                         bool defer_fix = false)
 {
 	WM_PROF("align.update_extra");   // mm_update_extra, src/align.c:240-286 (no =/X rewriting: MM_F_EQX is applied at output time if requested)
 	if (!r.has_p) return;
+	if (pend && defer_fix) {
+		pend->on = pend->fix = true; pend->qp = qseq; pend->tp = tseq; pend->q_pos = q_pos; pend->rid = rid; pend->t_pos = t_pos;
+		return;
+	}
 	int qshift, tshift;
 	fix_cigar(r, qseq, tseq, &qshift, &tshift);
 	qseq += qshift, tseq += tshift;
@@ -773,7 +738,7 @@ static void finish_reg(const AlnEnv &E, RegAln &A, m128 *a, const std::vector<Ks
 	if (r.has_p) {
 		WM_INVARIANT(rs1 >= A.rs0 && re1 <= A.re0);
 		const uint8_t *q0 = E.qseq0[r.rev] + qs1;
-		update_extra(r, q0, A.tbuf.data() + (rs1 - A.rs0), E.mat, opt.q, opt.e, E.defer_extra ? &A.xp : 0, (int32_t)(q0 - E.qseq0[0]), A.rid, rs1);
+		update_extra(r, q0, A.tbuf.data() + (rs1 - A.rs0), E.mat, opt.q, opt.e, E.defer_extra ? &A.xp : 0, (int32_t)(q0 - E.qseq0[0]), A.rid, rs1, E.defer_fix);
 	}
 }
 
@@ -818,7 +783,7 @@ static bool align_inv(Scheduler &sch, const AlnEnv &E, const Reg &r1, const Reg 
 	r_inv.rs = r1.re + t_off;
 	r_inv.re = r_inv.rs + j.ez.max_t + 1;
 	// (qstart may lie up to 7 bases in front of its strand: in two-strand space the tail of the other strand, or the N padding in front of strand 0)
-	update_extra(r_inv, qstart, &tseq[t_off], E.mat, opt.q, opt.e, E.defer_extra ? &xp : 0, (int32_t)(qstart - E.qseq0[0]), r1.rid, r1.re + t_off);
+	update_extra(r_inv, qstart, &tseq[t_off], E.mat, opt.q, opt.e, E.defer_extra ? &xp : 0, (int32_t)(qstart - E.qseq0[0]), r1.rid, r1.re + t_off, E.defer_fix);
 	if (xp.on) keep_t = std::move(tseq);                               // (a moved vector keeps its storage: xp.tp stays valid)
 	return true;
 }
@@ -827,7 +792,8 @@ void align_skeleton(Scheduler &sch, const MapOpt &opt, const Index &idx, int qle
 {
 	AlnEnv E;
 	E.opt = &opt; E.idx = &idx; E.qlen = qlen; E.q_dev_off = q_dev_off; E.q_has_n = false;
-	E.defer_extra = sch.extra_deferred();
+	E.defer_fix = sch.fix_deferred();
+	E.defer_extra = E.defer_fix || sch.extra_deferred();
 	// both strands in ONE buffer, reverse complement right behind the forward strand, exactly like the reference's
 	// qseq0 (src/align.c:871-877): mm_align1_inv may step a few bases in front of a strand (see align_inv)
 	// (three flat loops the compiler vectorises — a copy, a reversed complement, an OR-reduction — instead of one byte loop with two branches:
@@ -858,6 +824,21 @@ void align_skeleton(Scheduler &sch, const MapOpt &opt, const Index &idx, int qle
 	struct Deferred { Reg *r; ExtraPend p; };
 	std::vector<Deferred> deferred;
 	std::list<std::vector<uint8_t>> keep_t;
+	// mm_align1_inv reads qs / qe / rs / re of both its neighbours (src/align.c:906-911), which mm_fix_cigar may move: a neighbour whose fix still waits gets it
+	// here and now, on the host, and its record degrades to scan-only. (Nothing else between finish_reg and the request reads a region's CIGAR or coordinates.)
+	auto fix_now = [&](Reg *r) {
+		for (size_t i = deferred.size(); i-- > 0;) {
+			ExtraPend &p = deferred[i].p;
+			if (deferred[i].r != r) continue;
+			if (p.fix) {
+				int qshift, tshift;
+				fix_cigar(*r, p.qp, p.tp, &qshift, &tshift);
+				p.qp += qshift; p.tp += tshift; p.q_pos += qshift; p.t_pos += tshift; p.fix = false;
+				++fix_stats().early;
+			}
+			break;
+		}
+	};
 	for (;;) {
 		std::vector<std::list<Node>::iterator> todo;
 		for (auto it = L.begin(); it != L.end(); ++it) if (it->pending) todo.push_back(it);
@@ -892,31 +873,48 @@ void align_skeleton(Scheduler &sch, const MapOpt &opt, const Index &idx, int qle
 			} else if (is_splice && A[k].r.has_p) A[k].r.trans_strand = (opt.flag & F_SPLICE_FOR) ? 1 : 2;
 			auto it = todo[k];
 			it->r = std::move(A[k].r); it->pending = false;
-			if (A[k].xp.on) { keep_t.push_back(std::move(A[k].tbuf)); deferred.push_back(Deferred{ &it->r, A[k].xp }); }
+			if (A[k].xp.on) { keep_t.push_back(std::move(A[k].tbuf)); deferred.push_back(Deferred{ &it->r, A[k].xp }); if (A[k].xp.fix) ++fix_stats().deferred; }
 			auto after = std::next(it);
 			// inversion rescue between this piece and its predecessor (src/align.c:906-911)
 			if (it != L.begin() && it->r.split_inv) {
 				Reg inv; ExtraPend ip; std::vector<uint8_t> inv_t;
+				if (E.defer_fix) { fix_now(&std::prev(it)->r); fix_now(&it->r); }
 				if (align_inv(sch, E, std::prev(it)->r, it->r, inv, ip, inv_t)) {
 					auto at = L.insert(after, Node{ std::move(inv), false });
-					if (ip.on) { keep_t.push_back(std::move(inv_t)); deferred.push_back(Deferred{ &at->r, ip }); }
+					if (ip.on) { keep_t.push_back(std::move(inv_t)); deferred.push_back(Deferred{ &at->r, ip }); if (ip.fix) ++fix_stats().deferred; }
 				}
 			}
 			if (A[k].r2.cnt > 0) L.insert(after, Node{ std::move(A[k].r2), true });
 		}
 	}
 	if (!deferred.empty()) {          // nothing above reads blen, mlen, dp_max or n_ambi: one batched request for the whole read, just before filter_regs does
-		std::vector<ExtraReq> xr(deferred.size());
-		for (size_t i = 0; i < xr.size(); ++i) {
+		std::vector<ExtraReq> xr; std::vector<FixReq> fr;
+		std::vector<size_t> xi, fi;
+		xr.reserve(deferred.size()); fr.reserve(deferred.size());
+		const wm_extra_score_t sc = { E.mat[0], E.mat[1], E.mat[24], opt.q, opt.e };
+		for (size_t i = 0; i < deferred.size(); ++i) {
 			const Deferred &d = deferred[i];
-			ExtraReq &x = xr[i];
-			x.qp = d.p.qp; x.tp = d.p.tp; x.qwin_off = E.q_dev_off; x.qwin_len = qlen; x.q_pos = d.p.q_pos; x.rid = d.p.rid; x.t_pos = d.p.t_pos;
-			x.cigar = d.r->cigar.data(); x.n_cigar = (int)d.r->cigar.size();
-			x.sc.match = E.mat[0]; x.sc.mismatch = E.mat[1]; x.sc.ambi = E.mat[24]; x.sc.q = opt.q; x.sc.e = opt.e;
+			if (d.p.fix) {          // both halves: the stitched CIGAR goes out, the fixed one and both shifts come back
+				fr.emplace_back(); fi.push_back(i);
+				FixReq &x = fr.back();
+				x.qp = d.p.qp; x.tp = d.p.tp; x.qwin_off = E.q_dev_off; x.qwin_len = qlen; x.q_pos = d.p.q_pos; x.rid = d.p.rid; x.t_pos = d.p.t_pos;
+				x.cigar = &d.r->cigar; x.sc = sc;
+			} else {
+				xr.emplace_back(); xi.push_back(i);
+				ExtraReq &x = xr.back();
+				x.qp = d.p.qp; x.tp = d.p.tp; x.qwin_off = E.q_dev_off; x.qwin_len = qlen; x.q_pos = d.p.q_pos; x.rid = d.p.rid; x.t_pos = d.p.t_pos;
+				x.cigar = d.r->cigar.data(); x.n_cigar = (int)d.r->cigar.size(); x.sc = sc;
+			}
 		}
 		extra_stats().deferred += xr.size();
-		sch.extra(xr);
-		for (size_t i = 0; i < xr.size(); ++i) store_extra(*deferred[i].r, xr[i].out);
+		sch.fix_extra(fr, xr);
+		for (size_t i = 0; i < xr.size(); ++i) store_extra(*deferred[xi[i]].r, xr[i].out);
+		for (size_t i = 0; i < fr.size(); ++i) {
+			Reg &r = *deferred[fi[i]].r;
+			if (r.rev) r.qe -= fr[i].qshift; else r.qs += fr[i].qshift;
+			r.rs += fr[i].tshift;
+			store_extra(r, fr[i].out);
+		}
 	}
 	regs.clear();
 	for (Node &n : L) regs.push_back(std::move(n.r));

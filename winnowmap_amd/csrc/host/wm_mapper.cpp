@@ -241,6 +241,7 @@ void map_batch(const Index &idx, const MapOpt &opt, DeviceOps *ops, const std::v
 	const size_t window = std::max<size_t>(1, (size_t)(inflight_env > 0 ? inflight_env : 16384) / (size_t)T);
 	Hub hub(ops, sc, idx.w, idx.k);
 	hub.extra_dev = extra_device_on();          // (read when the mapping call starts: wm_set_extra_device / WM_EXTRA_DEV)
+	hub.fix_dev = fix_device_on();              // (... wm_set_fix_device / WM_FIX_DEV)
 	hub.n_workers = T;
 	hub.max_sw_mat = opt.max_sw_mat;
 	hub.splice = (opt.flag & F_SPLICE) != 0; hub.noncan = opt.noncan; hub.junc_bonus = opt.junc_bonus;

@@ -1,7 +1,8 @@
-// wm_ops.cpp — DeviceOps::window_batch composed from the per-operation batches, the host form of DeviceOps::extra_batch and the switch + account of
+// wm_ops.cpp — DeviceOps::window_batch composed from the per-operation batches, the host forms of DeviceOps::extra_batch / fix_extra_batch and the switches + accounts of
 // the deferred final scans (see wm_ops.h).
 #include "wm_ops.h"
 #include "wm_sdust.h"
+#include "../cigar_fix.h"
 
 namespace wm {
 
@@ -85,9 +86,52 @@ void DeviceOps::extra_batch(const wm_extra_score_t &sc, std::vector<ExtraReq*> &
 	extra_stats().on_host += reqs.size();
 }
 
+// ---- mm_fix_cigar + the scan as one deferred, batched operation -------------------------------------------------------------------------------
+static std::atomic<int> g_fix_dev(-1);            // -1: the environment decides (WM_FIX_DEV), read whenever a mapping call starts
+bool fix_device_on()
+{
+	const int v = g_fix_dev.load(std::memory_order_relaxed);
+	if (v >= 0) return v != 0;
+	const char *e = getenv("WM_FIX_DEV");
+	return e && atoi(e) != 0;
+}
+FixStats &fix_stats() { static FixStats s; return s; }
+// WM_EXTRA_REPORT=1: this account too
+static struct FixReport {
+	~FixReport()
+	{
+		FixStats &s = fix_stats();
+		if (!getenv("WM_EXTRA_REPORT") || !s.deferred.load()) return;
+		fprintf(stderr, "[wm] fix: %llu regions deferred, %llu fixed on the device, %llu on the host, %llu early on the host (inversion test), %llu batched calls, %llu us inside the calls, %llu columns\n",
+		        (unsigned long long)s.deferred.load(), (unsigned long long)s.on_device.load(), (unsigned long long)s.on_host.load(), (unsigned long long)s.early.load(),
+		        (unsigned long long)s.calls.load(), (unsigned long long)s.us.load(), (unsigned long long)s.cols.load());
+	}
+} g_fix_report;
+
+void DeviceOps::fix_extra_batch(const wm_extra_score_t &sc, std::vector<FixReq*> &reqs)
+{
+	WM_SITE("fix.host");
+	parallel_for(1, reqs.size(), [&](size_t i) {
+		FixReq &r = *reqs[i];
+		int n = (int)r.cigar->size(), qs = 0, ts = 0;
+		if (n > 1) { wm_fix_cigar(r.cigar->data(), &n, r.qp, r.tp, &qs, &ts, 0, 0); r.cigar->resize((size_t)n); }
+		r.qshift = qs; r.tshift = ts;
+		extra_walk_host(r.qp + qs, r.tp + ts, r.cigar->data(), n, sc.match, sc.mismatch, sc.ambi, sc.q, sc.e, &r.out);
+	});
+	fix_stats().on_host += reqs.size();
+}
+
 } // namespace wm
 
 extern "C" {
+void wm_set_fix_device(int on) { wm::g_fix_dev = on < 0 ? -1 : on ? 1 : 0; }
+int wm_fix_device_enabled(void) { return wm::fix_device_on() ? 1 : 0; }
+void wm_fix_stats(uint64_t *out7, int reset)
+{
+	wm::FixStats &s = wm::fix_stats();
+	std::atomic<uint64_t> *f[7] = { &s.deferred, &s.on_device, &s.on_host, &s.early, &s.calls, &s.us, &s.cols };
+	for (int i = 0; i < 7; ++i) { if (out7) out7[i] = f[i]->load(); if (reset) f[i]->store(0); }
+}
 void wm_set_extra_device(int on) { wm::g_extra_dev = on < 0 ? -1 : on ? 1 : 0; }
 int wm_extra_device_enabled(void) { return wm::extra_device_on() ? 1 : 0; }
 void wm_extra_stats(uint64_t *out6, int reset)

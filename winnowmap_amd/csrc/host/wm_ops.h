@@ -94,6 +94,16 @@ struct ExtraReq {                  // the scan of mm_update_extra (src/align.c:2
 	wm_extra_t out = { 0, 0, 0, 0, 0, 0 };                 // out
 	bool resident() const { return qwin_off >= 0 && rid >= 0; }
 };
+struct FixReq {                    // mm_update_extra as a whole (src/align.c:240-286): mm_fix_cigar (:91-167) on a region's STITCHED CIGAR, then the scan of what it leaves
+	// host views and positions of both operands from the first base of the STITCHED alignment on, the rules of ExtraReq
+	const uint8_t *qp = 0, *tp = 0;
+	int64_t qwin_off = -1; int32_t qwin_len = 0, q_pos = 0, rid = -1, t_pos = 0;
+	std::vector<uint32_t> *cigar = 0;                      // in: the stitched CIGAR; out: the fixed one (the region's own vector)
+	wm_extra_score_t sc = { 0, 0, 0, 0, 0 };
+	int32_t qshift = 0, tshift = 0;                        // out: the leading I / D that went (the mapper moves qs / qe / rs)
+	wm_extra_t out = { 0, 0, 0, 0, 0, 0 };                 // out: the scan of the fixed CIGAR, operands advanced by both shifts
+	bool resident() const { return qwin_off >= 0 && rid >= 0; }
+};
 // wm_extra_walk (csrc/cigar_walk.h), 16 bases per step where the build has SSE2 and match > 0 (host/wm_align.cpp)
 void extra_walk_host(const uint8_t *qseq, const uint8_t *tseq, const uint32_t *cigar, int n_cigar, int match, int mismatch, int ambi, int q, int e, wm_extra_t *out);
 
@@ -102,6 +112,12 @@ void extra_walk_host(const uint8_t *qseq, const uint8_t *tseq, const uint32_t *c
 bool extra_device_on();
 struct ExtraStats { std::atomic<uint64_t> deferred{0}, on_device{0}, on_host{0}, calls{0}, cols{0}, us{0}; };
 ExtraStats &extra_stats();
+
+// The switch for BOTH halves (wm_set_fix_device / WM_FIX_DEV; off by default) and its account (wm_fix_stats): regions whose fix was deferred, fixed on the device, fixed
+// on the host by the batched request, fixed on the host early because an inversion test was about to read them, batched device calls, microseconds inside them, alignment columns the fused calls walked.
+bool fix_device_on();
+struct FixStats { std::atomic<uint64_t> deferred{0}, on_device{0}, on_host{0}, early{0}, calls{0}, us{0}, cols{0}; };
+FixStats &fix_stats();
 
 // The batch calls are synchronous (they return when the results are in the requests) and must be callable from several threads at
 // once: the hub (wm_fiber.h) keeps up to max_inflight() of them running concurrently.
@@ -126,6 +142,9 @@ struct DeviceOps {
 	// the deferred final scans of a mapping call's regions (the switch above). The default walks them on the host (wm_extra_walk / its SSE form) — checker-backed
 	// implementations need nothing; the product's GpuOps overrides it with wm_extra_batch_pos when every request is resident.
 	virtual void extra_batch(const wm_extra_score_t &sc, std::vector<ExtraReq*> &reqs);
+	// ... and both halves of mm_update_extra for regions that kept their stitched CIGAR (the switch above). The default runs the specification (csrc/cigar_fix.h) and the
+	// host walk; the product's GpuOps overrides it with wm_fix_extra_batch_pos when every request is resident and the call would not be refused.
+	virtual void fix_extra_batch(const wm_extra_score_t &sc, std::vector<FixReq*> &reqs);
 	// the whole window in one call. The default composes it from the three operations above (checker-backed implementations in the
 	// test-suite); the product's GpuOps overrides it with the HBM-resident wm_window_batch.
 	virtual void window_batch(int w, int k, std::vector<WindowReq*> &reqs);

@@ -279,6 +279,55 @@ struct GpuOpsCtx {
 		st.on_device += (uint64_t)n; ++st.calls; st.cols += cols; st.us += (uint64_t)((now_ms() - t0) * 1e3);
 		return true;
 	}
+	// both halves of mm_update_extra (src/align.c:240-286 with mm_fix_cigar, :91-167) through wm_fix_extra_batch_pos: the stitched CIGARs go out, the fixed ones, both shifts
+	// and the scan come back. Returns false — nothing done, nothing touched — unless every request is resident and the call would not refuse an op (a zero-length op
+	// of code >= 3; the aligner writes none); the caller then runs the host form. (A job over WM_EXTRA_MAX_ABS or 2^31 summed lengths is refused by the call and fails
+	// the mapping call, exactly as extra_batch does: finding it beforehand would cost the measuring pass a second time.)
+	bool fix_extra_batch(const wm_extra_score_t &sc, std::vector<wm::FixReq*> &reqs)
+	{
+		const int n = (int)reqs.size();
+		if (!resident) return false;
+		for (int i = 0; i < n; ++i) if (!reqs[i]->resident()) return false;
+		const double t0 = now_ms();
+		std::vector<wm_extra_pos_t> jobs(n);
+		size_t tot = 0;
+		for (int i = 0; i < n; ++i) {
+			const wm::FixReq &r = *reqs[i];
+			wm_extra_pos_t &j = jobs[i];
+			j.qwin_off = r.qwin_off; j.qwin_len = r.qwin_len; j.q_pos = r.q_pos; j.rid = r.rid; j.t_pos = r.t_pos; j.cig_off = (uint32_t)tot; j.n_cigar = (int32_t)r.cigar->size();
+			tot += r.cigar->size();
+		}
+		if (tot >= ((size_t)1 << 31)) { error = "fix batch exceeds 2^31 CIGAR ops"; return true; }
+		UBuf<uint32_t> cig(2 * (tot + 1), c);
+		uint32_t *cig_out = cig.data() + tot + 1;
+		std::atomic<int> refusable(0);
+		WM_SITE("fix.cigars");
+		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) {
+			const std::vector<uint32_t> &cg = *reqs[i]->cigar;
+			if (cg.empty()) return;
+			memcpy(cig.data() + jobs[i].cig_off, cg.data(), cg.size() * 4);
+			uint32_t bad = 0;
+			for (size_t k = 0; k < cg.size(); ++k) bad |= (uint32_t)(cg[k] - 3u < 13u);          // (length 0 and code >= 3: the word is 3 .. 15)
+			if (bad) refusable = 1;
+		});
+		if (refusable.load()) return false;
+		std::vector<wm_extra_res_t> res(n);
+		std::vector<wm_fix_res_t> fr(n);
+		if (wm_fix_extra_batch_pos(c, &sc, n, jobs.data(), cig.data(), tot, cig_out, fr.data(), res.data())) { fail("fix"); return true; }
+		WM_SITE("fix.unpack");
+		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) {
+			wm::FixReq &r = *reqs[i];
+			if (fr[i].changed) r.cigar->assign(cig_out + jobs[i].cig_off, cig_out + jobs[i].cig_off + fr[i].n_cigar);
+			r.qshift = fr[i].qshift; r.tshift = fr[i].tshift;
+			memcpy(&r.out, &res[i], sizeof(wm_extra_t));
+		});
+		uint64_t cols = 0;
+		for (int i = 0; i < n; ++i) cols += (uint64_t)(res[i].blen + res[i].n_ambi);
+		wm::FixStats &st = wm::fix_stats();
+		st.on_device += (uint64_t)n; ++st.calls; st.us += (uint64_t)((now_ms() - t0) * 1e3);
+		st.cols += cols;
+		return true;
+	}
 	// splice mode (src/align.c:326-327): the requests through wm_ksw_exts2_batch, in groups whose unbanded traceback matrices fit the arena
 	void exts2_batch(const wm_ksw_score_t &sc, int noncan, int junc_bonus, std::vector<wm::KswReq*> &reqs)
 	{
@@ -454,6 +503,13 @@ struct GpuOps {                          // the device contexts of a mapper, sha
 		*served = false;
 		with(e, [&](GpuOpsCtx &x) { bool all = true; run_split(x, reqs, [&](std::vector<wm::ExtraReq*> &part) { all = x.extra_batch(sc, part) && all; }); *served = all; });
 	}
+	// rest: the requests of parts that were not served (not resident, or refusable); they are untouched
+	void fix_extra_batch(wm::ErrorSink &e, const wm_extra_score_t &sc, std::vector<wm::FixReq*> &reqs, std::vector<wm::FixReq*> &rest)
+	{
+		bool ran = false;
+		with(e, [&](GpuOpsCtx &x) { ran = true; run_split(x, reqs, [&](std::vector<wm::FixReq*> &part) { if (!x.fix_extra_batch(sc, part)) rest.insert(rest.end(), part.begin(), part.end()); }); });
+		if (!ran) rest = reqs;
+	}
 	// collect_seed_hits takes one (max_occ, flag) per call: the mapper's requests of one mapping call all share them
 	void window_batch(wm::ErrorSink &e, std::vector<wm::WindowReq*> &reqs) { with(e, [&](GpuOpsCtx &x) { run_split(x, reqs, [&](std::vector<wm::WindowReq*> &part) { x.window_batch(part); }); }); }
 };
@@ -485,6 +541,12 @@ struct CallOps : wm::DeviceOps {
 		bool served = false;
 		g.extra_batch(err, sc, reqs, &served);
 		if (!served) wm::DeviceOps::extra_batch(sc, reqs);          // a request that is not resident: the host walk (counted by wm_extra_stats)
+	}
+	void fix_extra_batch(const wm_extra_score_t &sc, std::vector<wm::FixReq*> &reqs) override
+	{
+		std::vector<wm::FixReq*> rest;
+		g.fix_extra_batch(err, sc, reqs, rest);
+		if (!rest.empty()) wm::DeviceOps::fix_extra_batch(sc, rest);       // not resident: the host specification + walk (counted by wm_fix_stats)
 	}
 };
 

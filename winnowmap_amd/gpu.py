@@ -167,6 +167,36 @@ class Context:
         _chk(lib().wm_extra_batch_pos(self._h, sc.ctypes.data, len(jobs), jobs.ctypes.data, cigars.ctypes.data, len(cigars), out.ctypes.data))
         return out
 
+    # ---- mm_fix_cigar on stitched CIGARs, fused with that scan ------------------------------------------
+    def fix_extra_batch(self, score, jobs, seqs, cigars):
+        """wm_fix_extra_batch: cigars = the stitched CIGARs; score = (match, mismatch, ambi, q, e) or None for the fix alone. Returns (cigars_out, fix, extra):
+        job i's fixed CIGAR is cigars_out[cig_off : cig_off + fix[i, 0]]; fix = int32 [n, 4] = n_cigar, qshift, tshift, changed; extra = int32 [n, 6] as
+        extra_batch gives for the fixed CIGAR with the operands advanced by both shifts (None without a score)."""
+        jobs = np.ascontiguousarray(jobs, EXTRA_JOB_DTYPE)
+        seqs = np.ascontiguousarray(seqs, np.uint8)
+        cigars = np.ascontiguousarray(cigars, np.uint32)
+        sc = None if score is None else np.array(score, np.int32)
+        assert sc is None or sc.shape == (5,)
+        out = np.zeros(len(cigars), np.uint32); fix = np.zeros((len(jobs), 4), np.int32)
+        extra = None if sc is None else np.zeros((len(jobs), 6), np.int32)
+        lib().wm_fix_extra_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        _chk(lib().wm_fix_extra_batch(self._h, None if sc is None else sc.ctypes.data, len(jobs), jobs.ctypes.data, seqs.ctypes.data, seqs.nbytes, cigars.ctypes.data,
+                                      len(cigars), out.ctypes.data, fix.ctypes.data, None if extra is None else extra.ctypes.data))
+        return out, fix, extra
+
+    def fix_extra_batch_pos(self, score, jobs, cigars):
+        """wm_fix_extra_batch_pos: jobs: structured array EXTRA_POS_DTYPE (operands as positions in the resident reads, two-strand space, and the uploaded reference)"""
+        jobs = np.ascontiguousarray(jobs, EXTRA_POS_DTYPE)
+        cigars = np.ascontiguousarray(cigars, np.uint32)
+        sc = None if score is None else np.array(score, np.int32)
+        assert sc is None or sc.shape == (5,)
+        out = np.zeros(len(cigars), np.uint32); fix = np.zeros((len(jobs), 4), np.int32)
+        extra = None if sc is None else np.zeros((len(jobs), 6), np.int32)
+        lib().wm_fix_extra_batch_pos.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        _chk(lib().wm_fix_extra_batch_pos(self._h, None if sc is None else sc.ctypes.data, len(jobs), jobs.ctypes.data, cigars.ctypes.data, len(cigars), out.ctypes.data,
+                                          fix.ctypes.data, None if extra is None else extra.ctypes.data))
+        return out, fix, extra
+
     def seed_batch_keyed(self, mini, mini_off, n_mini, qlen, keys, max_occ, flag, out_cap):
         """wm_seed_batch_keyed: collect_seed_hits with skip_seed's name comparison (src/map.c:132-154). mini: uint64 [n_total, 2]; keys: uint32 [n, 2]
         from Index.query_keys (None = wm_seed_batch: MM_F_NO_DIAG / MM_F_NO_DUAL are ignored). Returns (anchors uint64 [out_cap, 2], out_off, n_anchors, rep_len)."""
@@ -318,6 +348,32 @@ def extra_stats(reset=False):
     lib().wm_extra_stats.restype = None
     lib().wm_extra_stats(out.ctypes.data, 1 if reset else 0)
     return dict(zip(EXTRA_STAT_NAMES, (int(x) for x in out)))
+
+
+FIX_STAT_NAMES = ("deferred", "on_device", "on_host", "early_on_host", "calls", "device_us", "columns")
+
+
+def set_fix_device(on):
+    """wm_set_fix_device: the mapper defers BOTH halves of mm_update_extra — mm_fix_cigar and the scan — to one batched wm_fix_extra_batch_pos per read (off by
+    default; on < 0: back to what WM_FIX_DEV in the environment says). Read when a mapping call starts; results never depend on it."""
+    lib().wm_set_fix_device.argtypes = [C.c_int]
+    lib().wm_set_fix_device.restype = None
+    lib().wm_set_fix_device(int(on))
+
+
+def fix_device_enabled():
+    lib().wm_fix_device_enabled.restype = C.c_int
+    return bool(lib().wm_fix_device_enabled())
+
+
+def fix_stats(reset=False):
+    """wm_fix_stats: regions whose fix was deferred / fixed on the device / fixed on the host by the batched request / fixed on the host early because an inversion
+    test read them, batched device calls, microseconds, alignment columns walked by those calls"""
+    out = np.zeros(7, np.uint64)
+    lib().wm_fix_stats.argtypes = [C.c_void_p, C.c_int]
+    lib().wm_fix_stats.restype = None
+    lib().wm_fix_stats(out.ctypes.data, 1 if reset else 0)
+    return dict(zip(FIX_STAT_NAMES, (int(x) for x in out)))
 
 
 def set_ksw_routing(on=-1, rows4=-1, rows8=-1):
