@@ -180,6 +180,29 @@ int wm_fix_device_enabled(void);
  * mapping call, as it does for wm_extra_batch_pos under wm_set_extra_device; only a request that is not resident, or holds a zero-length op of code >= 3, falls through
  * to the host form. */
 void wm_fix_stats(uint64_t *out7, int reset);
+/* mm_update_cigar_eqx (src/align.c:169-238), the tail of mm_update_extra under MM_F_EQX (:285), over FINAL CIGARs as a batch: every M op becomes its runs of
+ * '=' (code 7) and 'X' (code 8), exactly as wm_cigar_eqx of csrc/cigar_eqx.h does (the specification; kernels: csrc/eqx_kernel.h). A run is a maximal stretch of
+ * columns of one M op with equal, or with unequal, codes (N against N is '='); n_EQX = runs of the CIGAR, n_M = its ops of code 0. If n_EQX == n_M the reference
+ * relabels every M op as '=' in place without looking again (:195-201) — also an M op that is all mismatches, also with a zero-length M op balancing an extra run —
+ * and so does this call (in_place = 1); otherwise every M op is replaced by its runs, a zero-length M op vanishes, every other op is copied as it stands.
+ * Jobs, operands and cigars as for wm_extra_batch[_pos] (the operands already advanced by mm_fix_cigar's shifts). Job i's new CIGAR lies at cigars_out + out[i].off
+ * and has out[i].n_cigar ops; the outputs lie back to back in job order. out_cap: ops cigars_out holds. WM_ENOMEM if it is too small: *out_used then holds the
+ * needed count and out[] is already filled (the rule of wm_ksw_batch's cigar_cap). n_cigar == 0 is valid and gives nothing. WM_EINVAL, naming the job, for what
+ * wm_extra_batch[_pos] refuses about operands and n_ops; there is no score, hence no score limit. Results do not depend on wm_extra_set_routing, whose two values
+ * route this call as well (a job's columns here are its M columns). */
+typedef struct { uint64_t off; int32_t n_cigar, in_place; } wm_eqx_res_t;
+int wm_eqx_batch(wm_ctx_t *ctx, int n_jobs, const wm_extra_job_t *jobs, const uint8_t *seqs, size_t seqs_bytes, const uint32_t *cigars, size_t n_ops,
+                 uint32_t *cigars_out, size_t out_cap, size_t *out_used, wm_eqx_res_t *out);
+int wm_eqx_batch_pos(wm_ctx_t *ctx, int n_jobs, const wm_extra_pos_t *jobs, const uint32_t *cigars, size_t n_ops,
+                     uint32_t *cigars_out, size_t out_cap, size_t *out_used, wm_eqx_res_t *out);
+/* The mapper's switch for that rewriting under MM_F_EQX: on = 1, it is deferred and goes out as one batched wm_eqx_batch_pos per read, after the read's scans
+ * (wherever they ran) and before the regions are filtered; 0 = the host form right behind every scan; < 0 = what WM_EQX_DEV in the environment says (read when a
+ * mapping call starts). OFF by default; without MM_F_EQX it does nothing. Results do not depend on it, nor on its two siblings above. */
+void wm_set_eqx_device(int on);
+int wm_eqx_device_enabled(void);
+/* out6: regions deferred, rewritten on the device, rewritten on the host by the batched request while the switch was on, batched device calls, M columns those
+ * calls walked, microseconds the mapper spent inside them — process-wide since the last reset. */
+void wm_eqx_stats(uint64_t *out6, int reset);
 
 /* diagnostics: per-phase cycle table of the stripe-pipelined wide-hull kernel; only in a library built with WM_KERNEL_DEFINES="WM_STRIPE_TIMING=1"
  * (WM_EINVAL otherwise). out16: cycles summed over wavefronts in scan / epoch set-up / cells / wait-left / bookkeeping / wait-right / publish, then rows,

@@ -162,6 +162,7 @@ struct AlnEnv {
 	bool q_has_n;
 	bool defer_fix = false;     // ... and their mm_fix_cigar with them (Scheduler::fix_deferred)
 	bool defer_extra = false;   // the regions' final scans wait for one batched request per read (Scheduler::extra_deferred)
+	int eqx = 0;                // MM_F_EQX: 1 = mm_update_cigar_eqx runs right after every scan (src/align.c:285), 2 = it waits for one batched request per read (Scheduler::eqx_deferred)
 };
 
 // one ksw request on query strand `rev`, strand coordinates [qs, qe), and reference [rs, re) of contig rid; `tb` = codes of the
@@ -469,7 +470,9 @@ void extra_walk_host(const uint8_t *qseq, const uint8_t *tseq, const uint32_t *c
 // align_skeleton sends the scans of all regions of the read as ONE batched request (Scheduler::extra); with it off the scan runs here, as it always did.
 // With the other switch on (fix_device_on) mm_fix_cigar waits as well: fix = true, the region keeps its STITCHED CIGAR and ExtraPend the operands of that — until
 // the batched request returns the fixed CIGAR and both shifts, or until an inversion test needs the region's coordinates (align_skeleton: fix_now).
-struct ExtraPend { bool on = false, fix = false; const uint8_t *qp = 0, *tp = 0; int32_t q_pos = 0, rid = -1, t_pos = 0; };
+// Under MM_F_EQX the rewriting of M into = / X follows the scan (src/align.c:285): at once (eqx = 1: here, or by the batched request that scans), or — with the third
+// switch on (eqx_device_on), eqx = 2 — as one more batched request per read after the scans' results are in (scanned = true: the scan ran here, only the rewriting waits).
+struct ExtraPend { bool on = false, fix = false, scanned = false; const uint8_t *qp = 0, *tp = 0; int32_t q_pos = 0, rid = -1, t_pos = 0; };
 
 static void store_extra(Reg &r, const wm_extra_t &x)
 {
@@ -478,24 +481,28 @@ static void store_extra(Reg &r, const wm_extra_t &x)
 	WM_INVARIANT(qoff == r.qe - r.qs && toff == r.re - r.rs);
 }
 
-// pend != 0: defer the scan. q_pos / rid / t_pos: where qseq[0] / tseq[0] sit in two-strand space / on the contig (the positions a device implementation reads)
-// defer_fix: mm_fix_cigar waits too
+// pend: where a deferred half leaves what it will read (unused when nothing waits). q_pos / rid / t_pos: where qseq[0] / tseq[0] sit in two-strand space / on the contig (the positions a device implementation reads)
+// defer_scan: the scan waits; defer_fix: mm_fix_cigar waits too; eqx: AlnEnv::eqx
 static void update_extra(Reg &r, const uint8_t *qseq, const uint8_t *tseq, const int8_t *mat, int q, int e, ExtraPend *pend = 0, int32_t q_pos = 0, int32_t rid = -1, int32_t t_pos = 0,
-                         bool defer_fix = false)
+                         bool defer_scan = false, bool defer_fix = false, int eqx = 0)
 {
-	WM_PROF("align.update_extra");   // mm_update_extra, src/align.c:240-286 (no =/X rewriting: MM_F_EQX is applied at output time if requested)
+	WM_PROF("align.update_extra");   // mm_update_extra, src/align.c:240-286, with mm_update_cigar_eqx (:169-238) as its tail under MM_F_EQX (:285)
 	if (!r.has_p) return;
-	if (pend && defer_fix) {
+	if (!defer_scan && eqx != 2) pend = 0;
+	if (pend && defer_scan && defer_fix) {
 		pend->on = pend->fix = true; pend->qp = qseq; pend->tp = tseq; pend->q_pos = q_pos; pend->rid = rid; pend->t_pos = t_pos;
 		return;
 	}
 	int qshift, tshift;
 	fix_cigar(r, qseq, tseq, &qshift, &tshift);
 	qseq += qshift, tseq += tshift;
-	if (pend) { pend->on = true; pend->qp = qseq; pend->tp = tseq; pend->q_pos = q_pos + qshift; pend->rid = rid; pend->t_pos = t_pos + tshift; return; }
+	if (pend) { pend->on = true; pend->qp = qseq; pend->tp = tseq; pend->q_pos = q_pos + qshift; pend->rid = rid; pend->t_pos = t_pos + tshift; }
+	if (pend && defer_scan) return;
 	wm_extra_t x;
 	extra_walk_host(qseq, tseq, r.cigar.data(), (int)r.cigar.size(), mat[0], mat[1], mat[24], q, e, &x);
 	store_extra(r, x);
+	if (eqx == 1) eqx_host(r.cigar, qseq, tseq);      // on the operands advanced by both shifts: "changes to qseq and tseq are not returned" (src/align.c:285)
+	else if (pend) pend->scanned = true;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -738,7 +745,7 @@ static void finish_reg(const AlnEnv &E, RegAln &A, m128 *a, const std::vector<Ks
 	if (r.has_p) {
 		WM_INVARIANT(rs1 >= A.rs0 && re1 <= A.re0);
 		const uint8_t *q0 = E.qseq0[r.rev] + qs1;
-		update_extra(r, q0, A.tbuf.data() + (rs1 - A.rs0), E.mat, opt.q, opt.e, E.defer_extra ? &A.xp : 0, (int32_t)(q0 - E.qseq0[0]), A.rid, rs1, E.defer_fix);
+		update_extra(r, q0, A.tbuf.data() + (rs1 - A.rs0), E.mat, opt.q, opt.e, &A.xp, (int32_t)(q0 - E.qseq0[0]), A.rid, rs1, E.defer_extra, E.defer_fix, E.eqx);
 	}
 }
 
@@ -783,7 +790,7 @@ static bool align_inv(Scheduler &sch, const AlnEnv &E, const Reg &r1, const Reg 
 	r_inv.rs = r1.re + t_off;
 	r_inv.re = r_inv.rs + j.ez.max_t + 1;
 	// (qstart may lie up to 7 bases in front of its strand: in two-strand space the tail of the other strand, or the N padding in front of strand 0)
-	update_extra(r_inv, qstart, &tseq[t_off], E.mat, opt.q, opt.e, E.defer_extra ? &xp : 0, (int32_t)(qstart - E.qseq0[0]), r1.rid, r1.re + t_off, E.defer_fix);
+	update_extra(r_inv, qstart, &tseq[t_off], E.mat, opt.q, opt.e, &xp, (int32_t)(qstart - E.qseq0[0]), r1.rid, r1.re + t_off, E.defer_extra, E.defer_fix, E.eqx);   // (the inversion's CIGAR is rewritten too, src/align.c:847)
 	if (xp.on) keep_t = std::move(tseq);                               // (a moved vector keeps its storage: xp.tp stays valid)
 	return true;
 }
@@ -794,6 +801,7 @@ void align_skeleton(Scheduler &sch, const MapOpt &opt, const Index &idx, int qle
 	E.opt = &opt; E.idx = &idx; E.qlen = qlen; E.q_dev_off = q_dev_off; E.q_has_n = false;
 	E.defer_fix = sch.fix_deferred();
 	E.defer_extra = E.defer_fix || sch.extra_deferred();
+	E.eqx = (opt.flag & F_EQX) ? (sch.eqx_deferred() ? 2 : 1) : 0;
 	// both strands in ONE buffer, reverse complement right behind the forward strand, exactly like the reference's
 	// qseq0 (src/align.c:871-877): mm_align1_inv may step a few bases in front of a strand (see align_inv)
 	// (three flat loops the compiler vectorises — a copy, a reversed complement, an OR-reduction — instead of one byte loop with two branches:
@@ -892,18 +900,20 @@ void align_skeleton(Scheduler &sch, const MapOpt &opt, const Index &idx, int qle
 		std::vector<size_t> xi, fi;
 		xr.reserve(deferred.size()); fr.reserve(deferred.size());
 		const wm_extra_score_t sc = { E.mat[0], E.mat[1], E.mat[24], opt.q, opt.e };
+		std::vector<std::pair<int32_t, int32_t>> shift(deferred.size(), std::make_pair(0, 0));      // what a deferred fix took off the front (the rewriting reads behind it)
 		for (size_t i = 0; i < deferred.size(); ++i) {
 			const Deferred &d = deferred[i];
+			if (d.p.scanned) continue;          // only the = / X rewriting waits
 			if (d.p.fix) {          // both halves: the stitched CIGAR goes out, the fixed one and both shifts come back
 				fr.emplace_back(); fi.push_back(i);
 				FixReq &x = fr.back();
 				x.qp = d.p.qp; x.tp = d.p.tp; x.qwin_off = E.q_dev_off; x.qwin_len = qlen; x.q_pos = d.p.q_pos; x.rid = d.p.rid; x.t_pos = d.p.t_pos;
-				x.cigar = &d.r->cigar; x.sc = sc;
+				x.cigar = &d.r->cigar; x.sc = sc; x.eqx = E.eqx == 1;
 			} else {
 				xr.emplace_back(); xi.push_back(i);
 				ExtraReq &x = xr.back();
 				x.qp = d.p.qp; x.tp = d.p.tp; x.qwin_off = E.q_dev_off; x.qwin_len = qlen; x.q_pos = d.p.q_pos; x.rid = d.p.rid; x.t_pos = d.p.t_pos;
-				x.cigar = d.r->cigar.data(); x.n_cigar = (int)d.r->cigar.size(); x.sc = sc;
+				x.cigar = d.r->cigar.data(); x.n_cigar = (int)d.r->cigar.size(); x.sc = sc; x.eqx = E.eqx == 1 ? &d.r->cigar : 0;
 			}
 		}
 		extra_stats().deferred += xr.size();
@@ -914,6 +924,20 @@ void align_skeleton(Scheduler &sch, const MapOpt &opt, const Index &idx, int qle
 			if (r.rev) r.qe -= fr[i].qshift; else r.qs += fr[i].qshift;
 			r.rs += fr[i].tshift;
 			store_extra(r, fr[i].out);
+			shift[fi[i]] = std::make_pair(fr[i].qshift, fr[i].tshift);
+		}
+		if (E.eqx == 2) {                  // every scan is in: one more batched request for the read, M -> runs of = / X (src/align.c:285)
+			std::vector<EqxReq> er(deferred.size());
+			for (size_t i = 0; i < deferred.size(); ++i) {
+				const Deferred &d = deferred[i];
+				EqxReq &x = er[i];
+				x.qp = d.p.qp + shift[i].first; x.tp = d.p.tp + shift[i].second; x.qwin_off = E.q_dev_off; x.qwin_len = qlen;
+				x.q_pos = d.p.q_pos + shift[i].first; x.rid = d.p.rid; x.t_pos = d.p.t_pos + shift[i].second;
+				x.cigar = &d.r->cigar;
+				x.cap_hint = (int32_t)std::min<int64_t>(INT32_MAX, (int64_t)d.r->cigar.size() + 2 * ((int64_t)d.r->blen - d.r->mlen + d.r->n_ambi));
+			}
+			eqx_stats().deferred += er.size();
+			sch.eqx(er);
 		}
 	}
 	regs.clear();

@@ -242,6 +242,7 @@ void map_batch(const Index &idx, const MapOpt &opt, DeviceOps *ops, const std::v
 	Hub hub(ops, sc, idx.w, idx.k);
 	hub.extra_dev = extra_device_on();          // (read when the mapping call starts: wm_set_extra_device / WM_EXTRA_DEV)
 	hub.fix_dev = fix_device_on();              // (... wm_set_fix_device / WM_FIX_DEV)
+	hub.eqx_dev = eqx_device_on();              // (... wm_set_eqx_device / WM_EQX_DEV; it only matters under MM_F_EQX)
 	hub.n_workers = T;
 	hub.max_sw_mat = opt.max_sw_mat;
 	hub.splice = (opt.flag & F_SPLICE) != 0; hub.noncan = opt.noncan; hub.junc_bonus = opt.junc_bonus;

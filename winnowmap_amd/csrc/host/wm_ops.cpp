@@ -3,6 +3,7 @@
 #include "wm_ops.h"
 #include "wm_sdust.h"
 #include "../cigar_fix.h"
+#include "../cigar_eqx.h"
 
 namespace wm {
 
@@ -82,6 +83,7 @@ void DeviceOps::extra_batch(const wm_extra_score_t &sc, std::vector<ExtraReq*> &
 	parallel_for(1, reqs.size(), [&](size_t i) {
 		ExtraReq &r = *reqs[i];
 		extra_walk_host(r.qp, r.tp, r.cigar, r.n_cigar, sc.match, sc.mismatch, sc.ambi, sc.q, sc.e, &r.out);
+		if (r.eqx) eqx_host(*r.eqx, r.qp, r.tp);                                 // src/align.c:285
 	});
 	extra_stats().on_host += reqs.size();
 }
@@ -96,7 +98,17 @@ bool fix_device_on()
 	return e && atoi(e) != 0;
 }
 FixStats &fix_stats() { static FixStats s; return s; }
-// WM_EXTRA_REPORT=1: this account too
+// WM_EXTRA_REPORT=1: this account too, and the one of the = / X rewriting
+static struct EqxReport {
+	~EqxReport()
+	{
+		EqxStats &s = eqx_stats();
+		if (!getenv("WM_EXTRA_REPORT") || !s.deferred.load()) return;
+		fprintf(stderr, "[wm] eqx: %llu regions deferred, %llu rewritten on the device, %llu on the host, %llu batched calls, %llu M columns, %llu us inside the calls\n",
+		        (unsigned long long)s.deferred.load(), (unsigned long long)s.on_device.load(), (unsigned long long)s.on_host.load(), (unsigned long long)s.calls.load(),
+		        (unsigned long long)s.cols.load(), (unsigned long long)s.us.load());
+	}
+} g_eqx_report;
 static struct FixReport {
 	~FixReport()
 	{
@@ -117,8 +129,42 @@ void DeviceOps::fix_extra_batch(const wm_extra_score_t &sc, std::vector<FixReq*>
 		if (n > 1) { wm_fix_cigar(r.cigar->data(), &n, r.qp, r.tp, &qs, &ts, 0, 0); r.cigar->resize((size_t)n); }
 		r.qshift = qs; r.tshift = ts;
 		extra_walk_host(r.qp + qs, r.tp + ts, r.cigar->data(), n, sc.match, sc.mismatch, sc.ambi, sc.q, sc.e, &r.out);
+		if (r.eqx) eqx_host(*r.cigar, r.qp + qs, r.tp + ts);                     // src/align.c:285
 	});
 	fix_stats().on_host += reqs.size();
+}
+
+// ---- mm_update_cigar_eqx: the host form, and the deferred, batched operation ----------------------------------------------------------------------
+int eqx_host(std::vector<uint32_t> &cigar, const uint8_t *qseq, const uint8_t *tseq)
+{
+	const int n = (int)cigar.size();
+	uint32_t n_M;
+	const uint32_t n_EQX = wm_cigar_eqx_count(cigar.data(), n, qseq, tseq, &n_M);
+	if (n_EQX == n_M) { wm_cigar_eqx_relabel(cigar.data(), n, cigar.data()); return 1; }
+	std::vector<uint32_t> out((size_t)n - n_M + n_EQX);
+	const int m = wm_cigar_eqx_rewrite(cigar.data(), n, qseq, tseq, out.data());
+	WM_INVARIANT((size_t)m == out.size());
+	cigar.swap(out);
+	return 0;
+}
+static std::atomic<int> g_eqx_dev(-1);            // -1: the environment decides (WM_EQX_DEV), read whenever a mapping call starts
+bool eqx_device_on()
+{
+	const int v = g_eqx_dev.load(std::memory_order_relaxed);
+	if (v >= 0) return v != 0;
+	const char *e = getenv("WM_EQX_DEV");
+	return e && atoi(e) != 0;
+}
+EqxStats &eqx_stats() { static EqxStats s; return s; }
+
+void DeviceOps::eqx_batch(std::vector<EqxReq*> &reqs)
+{
+	WM_SITE("eqx.host");
+	parallel_for(1, reqs.size(), [&](size_t i) {
+		EqxReq &r = *reqs[i];
+		r.in_place = eqx_host(*r.cigar, r.qp, r.tp) != 0;
+	});
+	eqx_stats().on_host += reqs.size();
 }
 
 } // namespace wm
@@ -131,6 +177,14 @@ void wm_fix_stats(uint64_t *out7, int reset)
 	wm::FixStats &s = wm::fix_stats();
 	std::atomic<uint64_t> *f[7] = { &s.deferred, &s.on_device, &s.on_host, &s.early, &s.calls, &s.us, &s.cols };
 	for (int i = 0; i < 7; ++i) { if (out7) out7[i] = f[i]->load(); if (reset) f[i]->store(0); }
+}
+void wm_set_eqx_device(int on) { wm::g_eqx_dev = on < 0 ? -1 : on ? 1 : 0; }
+int wm_eqx_device_enabled(void) { return wm::eqx_device_on() ? 1 : 0; }
+void wm_eqx_stats(uint64_t *out6, int reset)
+{
+	wm::EqxStats &s = wm::eqx_stats();
+	std::atomic<uint64_t> *f[6] = { &s.deferred, &s.on_device, &s.on_host, &s.calls, &s.cols, &s.us };
+	for (int i = 0; i < 6; ++i) { if (out6) out6[i] = f[i]->load(); if (reset) f[i]->store(0); }
 }
 void wm_set_extra_device(int on) { wm::g_extra_dev = on < 0 ? -1 : on ? 1 : 0; }
 int wm_extra_device_enabled(void) { return wm::extra_device_on() ? 1 : 0; }

@@ -92,6 +92,9 @@ struct ExtraReq {                  // the scan of mm_update_extra (src/align.c:2
 	const uint32_t *cigar = 0; int n_cigar = 0;            // the region's CIGAR (stays where it is until the request is served)
 	wm_extra_score_t sc = { 0, 0, 0, 0, 0 };               // mat[0], mat[1], mat[24], opt->q, opt->e: one value per mapping call
 	wm_extra_t out = { 0, 0, 0, 0, 0, 0 };                 // out
+	// MM_F_EQX with the rewriting not deferred (EqxReq below): the region's own vector (the same ops `cigar` points at), rewritten by mm_update_cigar_eqx
+	// (src/align.c:169-238, csrc/cigar_eqx.h) right after the scan, as the reference does (:285); 0 = no rewriting
+	std::vector<uint32_t> *eqx = 0;
 	bool resident() const { return qwin_off >= 0 && rid >= 0; }
 };
 struct FixReq {                    // mm_update_extra as a whole (src/align.c:240-286): mm_fix_cigar (:91-167) on a region's STITCHED CIGAR, then the scan of what it leaves
@@ -102,8 +105,20 @@ struct FixReq {                    // mm_update_extra as a whole (src/align.c:24
 	wm_extra_score_t sc = { 0, 0, 0, 0, 0 };
 	int32_t qshift = 0, tshift = 0;                        // out: the leading I / D that went (the mapper moves qs / qe / rs)
 	wm_extra_t out = { 0, 0, 0, 0, 0, 0 };                 // out: the scan of the fixed CIGAR, operands advanced by both shifts
+	bool eqx = false;                                      // MM_F_EQX, not deferred: mm_update_cigar_eqx on the fixed CIGAR after the scan (src/align.c:285), operands advanced by both shifts
 	bool resident() const { return qwin_off >= 0 && rid >= 0; }
 };
+struct EqxReq {                    // mm_update_cigar_eqx (src/align.c:169-238) over a region's FINAL CIGAR, deferred (the switch of wm_set_eqx_device): M -> runs of = / X
+	// host views and positions of both operands from the alignment's first base on, advanced by both shifts of mm_fix_cigar: the rules of ExtraReq
+	const uint8_t *qp = 0, *tp = 0;
+	int64_t qwin_off = -1; int32_t qwin_len = 0, q_pos = 0, rid = -1, t_pos = 0;
+	std::vector<uint32_t> *cigar = 0;                      // in: the final CIGAR; out: the rewritten one (the region's own vector)
+	int32_t cap_hint = 0;                                  // ops the result can have at most: n_ops + 2 x (blen - mlen + n_ambi) of the finished scan, every unequal column a run of its own plus the split it causes
+	bool in_place = false;                                 // out: the branch of src/align.c:195-201 ran
+	bool resident() const { return qwin_off >= 0 && rid >= 0; }
+};
+// mm_update_cigar_eqx on a vector (csrc/cigar_eqx.h); returns 1 if the in-place branch ran
+int eqx_host(std::vector<uint32_t> &cigar, const uint8_t *qseq, const uint8_t *tseq);
 // wm_extra_walk (csrc/cigar_walk.h), 16 bases per step where the build has SSE2 and match > 0 (host/wm_align.cpp)
 void extra_walk_host(const uint8_t *qseq, const uint8_t *tseq, const uint32_t *cigar, int n_cigar, int match, int mismatch, int ambi, int q, int e, wm_extra_t *out);
 
@@ -118,6 +133,12 @@ ExtraStats &extra_stats();
 bool fix_device_on();
 struct FixStats { std::atomic<uint64_t> deferred{0}, on_device{0}, on_host{0}, early{0}, calls{0}, us{0}, cols{0}; };
 FixStats &fix_stats();
+
+// The switch for the = / X rewriting under MM_F_EQX (wm_set_eqx_device / WM_EQX_DEV; off by default) and its account (wm_eqx_stats): regions deferred, rewritten on the
+// device, rewritten on the host by the batched request, batched device calls, M columns those calls walked, microseconds inside them.
+bool eqx_device_on();
+struct EqxStats { std::atomic<uint64_t> deferred{0}, on_device{0}, on_host{0}, calls{0}, cols{0}, us{0}; };
+EqxStats &eqx_stats();
 
 // The batch calls are synchronous (they return when the results are in the requests) and must be callable from several threads at
 // once: the hub (wm_fiber.h) keeps up to max_inflight() of them running concurrently.
@@ -145,6 +166,9 @@ struct DeviceOps {
 	// ... and both halves of mm_update_extra for regions that kept their stitched CIGAR (the switch above). The default runs the specification (csrc/cigar_fix.h) and the
 	// host walk; the product's GpuOps overrides it with wm_fix_extra_batch_pos when every request is resident and the call would not be refused.
 	virtual void fix_extra_batch(const wm_extra_score_t &sc, std::vector<FixReq*> &reqs);
+	// the deferred = / X rewriting of final CIGARs (MM_F_EQX with the switch above). The default runs the specification (csrc/cigar_eqx.h); the product's GpuOps
+	// overrides it with wm_eqx_batch_pos when every request is resident.
+	virtual void eqx_batch(std::vector<EqxReq*> &reqs);
 	// the whole window in one call. The default composes it from the three operations above (checker-backed implementations in the
 	// test-suite); the product's GpuOps overrides it with the HBM-resident wm_window_batch.
 	virtual void window_batch(int w, int k, std::vector<WindowReq*> &reqs);

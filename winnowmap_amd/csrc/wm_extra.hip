@@ -103,6 +103,7 @@ extern "C" void wm_extra_set_routing(int long_min_cols, int tile_cols)
 	if (tile_cols >= 64 && tile_cols % 64 == 0) g_extra_tile = tile_cols;
 }
 extern "C" int wm_extra_tile_cols(void) { return g_extra_tile.load(std::memory_order_relaxed); }
+int extra_long_min_cols() { return g_extra_long_min.load(std::memory_order_relaxed); }      // (for wm_eqx.hip, which is routed by the same two values)
 
 // ======================================================================================================
 // the batched call

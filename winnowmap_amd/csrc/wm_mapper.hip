@@ -275,6 +275,8 @@ struct GpuOpsCtx {
 			memcpy(&reqs[i]->out, &res[i], sizeof(wm_extra_t));
 			cols += (uint64_t)(res[i].blen + res[i].n_ambi);
 		}
+		// MM_F_EQX without its own switch: the rewriting follows the scan on the host (src/align.c:285), as in DeviceOps::extra_batch
+		if (n > 0 && reqs[0]->eqx) wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) { if (reqs[i]->eqx) wm::eqx_host(*reqs[i]->eqx, reqs[i]->qp, reqs[i]->tp); });
 		wm::ExtraStats &st = wm::extra_stats();
 		st.on_device += (uint64_t)n; ++st.calls; st.cols += cols; st.us += (uint64_t)((now_ms() - t0) * 1e3);
 		return true;
@@ -320,12 +322,53 @@ struct GpuOpsCtx {
 			if (fr[i].changed) r.cigar->assign(cig_out + jobs[i].cig_off, cig_out + jobs[i].cig_off + fr[i].n_cigar);
 			r.qshift = fr[i].qshift; r.tshift = fr[i].tshift;
 			memcpy(&r.out, &res[i], sizeof(wm_extra_t));
+			if (r.eqx) wm::eqx_host(*r.cigar, r.qp + r.qshift, r.tp + r.tshift);       // MM_F_EQX without its own switch: on the host, behind the scan (src/align.c:285)
 		});
 		uint64_t cols = 0;
 		for (int i = 0; i < n; ++i) cols += (uint64_t)(res[i].blen + res[i].n_ambi);
 		wm::FixStats &st = wm::fix_stats();
 		st.on_device += (uint64_t)n; ++st.calls; st.us += (uint64_t)((now_ms() - t0) * 1e3);
 		st.cols += cols;
+		return true;
+	}
+	// the deferred = / X rewriting (mm_update_cigar_eqx, src/align.c:169-238) through wm_eqx_batch_pos: the final CIGARs go out, the rewritten ones come back. Returns
+	// false — nothing done — unless every request is resident. The first capacity is the sum of the requests' cap_hint (a safe bound once the scan has run); should the
+	// call still report WM_ENOMEM for the pool, it is repeated once at the size it reported.
+	bool eqx_batch(std::vector<wm::EqxReq*> &reqs)
+	{
+		const int n = (int)reqs.size();
+		if (!resident) return false;
+		for (int i = 0; i < n; ++i) if (!reqs[i]->resident()) return false;
+		const double t0 = now_ms();
+		std::vector<wm_extra_pos_t> jobs(n);
+		size_t tot = 0, cap = 16;
+		for (int i = 0; i < n; ++i) {
+			const wm::EqxReq &r = *reqs[i];
+			wm_extra_pos_t &j = jobs[i];
+			j.qwin_off = r.qwin_off; j.qwin_len = r.qwin_len; j.q_pos = r.q_pos; j.rid = r.rid; j.t_pos = r.t_pos; j.cig_off = (uint32_t)tot; j.n_cigar = (int32_t)r.cigar->size();
+			tot += r.cigar->size();
+			cap += (size_t)std::max<int32_t>(r.cap_hint, (int32_t)std::min<size_t>(r.cigar->size(), INT32_MAX));
+		}
+		if (tot >= ((size_t)1 << 31)) { error = "eqx batch exceeds 2^31 CIGAR ops"; return true; }
+		UBuf<uint32_t> cig(tot + 1, c);
+		WM_SITE("eqx.cigars");
+		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) { if (!reqs[i]->cigar->empty()) memcpy(cig.data() + jobs[i].cig_off, reqs[i]->cigar->data(), reqs[i]->cigar->size() * 4); });
+		std::vector<wm_eqx_res_t> res(n);
+		std::vector<uint32_t> pool(cap);
+		size_t used = 0;
+		int rc = wm_eqx_batch_pos(c, n, jobs.data(), cig.data(), tot, pool.data(), cap, &used, res.data());
+		if (rc == WM_ENOMEM && used > cap) { cap = used; pool.resize(cap); rc = wm_eqx_batch_pos(c, n, jobs.data(), cig.data(), tot, pool.data(), cap, &used, res.data()); }
+		if (rc) { fail("eqx"); return true; }
+		WM_SITE("eqx.unpack");
+		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) {
+			wm::EqxReq &r = *reqs[i];
+			r.cigar->assign(pool.begin() + res[i].off, pool.begin() + res[i].off + res[i].n_cigar);
+			r.in_place = res[i].in_place != 0;
+		});
+		uint64_t cols = 0;
+		for (int i = 0; i < n; ++i) for (uint32_t w : *reqs[i]->cigar) if ((w & 0xf) == 7 || (w & 0xf) == 8) cols += w >> 4;
+		wm::EqxStats &st = wm::eqx_stats();
+		st.on_device += (uint64_t)n; ++st.calls; st.cols += cols; st.us += (uint64_t)((now_ms() - t0) * 1e3);
 		return true;
 	}
 	// splice mode (src/align.c:326-327): the requests through wm_ksw_exts2_batch, in groups whose unbanded traceback matrices fit the arena
@@ -510,6 +553,12 @@ struct GpuOps {                          // the device contexts of a mapper, sha
 		with(e, [&](GpuOpsCtx &x) { ran = true; run_split(x, reqs, [&](std::vector<wm::FixReq*> &part) { if (!x.fix_extra_batch(sc, part)) rest.insert(rest.end(), part.begin(), part.end()); }); });
 		if (!ran) rest = reqs;
 	}
+	void eqx_batch(wm::ErrorSink &e, std::vector<wm::EqxReq*> &reqs, std::vector<wm::EqxReq*> &rest)
+	{
+		bool ran = false;
+		with(e, [&](GpuOpsCtx &x) { ran = true; run_split(x, reqs, [&](std::vector<wm::EqxReq*> &part) { if (!x.eqx_batch(part)) rest.insert(rest.end(), part.begin(), part.end()); }); });
+		if (!ran) rest = reqs;
+	}
 	// collect_seed_hits takes one (max_occ, flag) per call: the mapper's requests of one mapping call all share them
 	void window_batch(wm::ErrorSink &e, std::vector<wm::WindowReq*> &reqs) { with(e, [&](GpuOpsCtx &x) { run_split(x, reqs, [&](std::vector<wm::WindowReq*> &part) { x.window_batch(part); }); }); }
 };
@@ -547,6 +596,12 @@ struct CallOps : wm::DeviceOps {
 		std::vector<wm::FixReq*> rest;
 		g.fix_extra_batch(err, sc, reqs, rest);
 		if (!rest.empty()) wm::DeviceOps::fix_extra_batch(sc, rest);       // not resident: the host specification + walk (counted by wm_fix_stats)
+	}
+	void eqx_batch(std::vector<wm::EqxReq*> &reqs) override
+	{
+		std::vector<wm::EqxReq*> rest;
+		g.eqx_batch(err, reqs, rest);
+		if (!rest.empty()) wm::DeviceOps::eqx_batch(rest);                 // not resident: the host specification (counted by wm_eqx_stats)
 	}
 };
 

@@ -197,6 +197,37 @@ class Context:
                                           fix.ctypes.data, None if extra is None else extra.ctypes.data))
         return out, fix, extra
 
+    # ---- mm_update_cigar_eqx over final CIGARs: M -> runs of = / X ----------------------------------------
+    def _eqx(self, fn, head, cigars, n_jobs, out_cap):
+        cigars = np.ascontiguousarray(cigars, np.uint32)
+        assert EQX_RES_DTYPE.itemsize == 16
+        if out_cap is None:          # every op, and one more per M column: what a CIGAR can become at most
+            out_cap = len(cigars) + int((cigars[(cigars & 0xf) == 0] >> 4).astype(np.int64).sum())
+        pool = np.zeros(max(int(out_cap), 1), np.uint32)
+        res = np.zeros(n_jobs, EQX_RES_DTYPE)
+        used = C.c_size_t(0)
+        rc = fn(*head, cigars.ctypes.data, len(cigars), pool.ctypes.data, int(out_cap), C.byref(used), res.ctypes.data)
+        if rc != 0:
+            e = WmError("libwmgpu error %d: %s" % (rc, lib().wm_last_error().decode()))
+            e.rc, e.needed, e.res = rc, used.value, res       # (WM_ENOMEM = -3: `needed` ops, res is already filled)
+            raise e
+        return pool[:used.value], res
+
+    def eqx_batch(self, jobs, seqs, cigars, out_cap=None):
+        """wm_eqx_batch: jobs: structured array EXTRA_JOB_DTYPE (operands as 0..4 codes inside seqs, advanced by mm_fix_cigar's shifts); cigars: the FINAL CIGARs.
+        Returns (pool, res): res = EQX_RES_DTYPE per job, job i's new CIGAR is pool[off : off + n_cigar], in_place = the branch of src/align.c:195-201 ran.
+        out_cap: ops the pool holds (None = a safe bound); too small raises WmError with .rc == -3, .needed and .res set."""
+        jobs = np.ascontiguousarray(jobs, EXTRA_JOB_DTYPE)
+        seqs = np.ascontiguousarray(seqs, np.uint8)
+        lib().wm_eqx_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+        return self._eqx(lib().wm_eqx_batch, (self._h, len(jobs), jobs.ctypes.data, seqs.ctypes.data, seqs.nbytes), cigars, len(jobs), out_cap)
+
+    def eqx_batch_pos(self, jobs, cigars, out_cap=None):
+        """wm_eqx_batch_pos: jobs: structured array EXTRA_POS_DTYPE (operands as positions in the resident reads, two-strand space, and the uploaded reference)"""
+        jobs = np.ascontiguousarray(jobs, EXTRA_POS_DTYPE)
+        lib().wm_eqx_batch_pos.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+        return self._eqx(lib().wm_eqx_batch_pos, (self._h, len(jobs), jobs.ctypes.data), cigars, len(jobs), out_cap)
+
     def seed_batch_keyed(self, mini, mini_off, n_mini, qlen, keys, max_occ, flag, out_cap):
         """wm_seed_batch_keyed: collect_seed_hits with skip_seed's name comparison (src/map.c:132-154). mini: uint64 [n_total, 2]; keys: uint32 [n, 2]
         from Index.query_keys (None = wm_seed_batch: MM_F_NO_DIAG / MM_F_NO_DUAL are ignored). Returns (anchors uint64 [out_cap, 2], out_off, n_anchors, rep_len)."""
@@ -374,6 +405,32 @@ def fix_stats(reset=False):
     lib().wm_fix_stats.restype = None
     lib().wm_fix_stats(out.ctypes.data, 1 if reset else 0)
     return dict(zip(FIX_STAT_NAMES, (int(x) for x in out)))
+
+
+EQX_RES_DTYPE = np.dtype([("off", np.uint64), ("n_cigar", np.int32), ("in_place", np.int32)])                                                 # wm_eqx_res_t
+EQX_STAT_NAMES = ("deferred", "on_device", "on_host", "calls", "columns", "device_us")
+
+
+def set_eqx_device(on):
+    """wm_set_eqx_device: under MM_F_EQX the mapper defers the = / X rewriting of final CIGARs (mm_update_cigar_eqx) to one batched wm_eqx_batch_pos per read (off
+    by default; on < 0: back to what WM_EQX_DEV in the environment says). Read when a mapping call starts; results never depend on it."""
+    lib().wm_set_eqx_device.argtypes = [C.c_int]
+    lib().wm_set_eqx_device.restype = None
+    lib().wm_set_eqx_device(int(on))
+
+
+def eqx_device_enabled():
+    lib().wm_eqx_device_enabled.restype = C.c_int
+    return bool(lib().wm_eqx_device_enabled())
+
+
+def eqx_stats(reset=False):
+    """wm_eqx_stats: regions deferred / rewritten on the device / rewritten on the host by the batched request, batched device calls, M columns, microseconds"""
+    out = np.zeros(6, np.uint64)
+    lib().wm_eqx_stats.argtypes = [C.c_void_p, C.c_int]
+    lib().wm_eqx_stats.restype = None
+    lib().wm_eqx_stats(out.ctypes.data, 1 if reset else 0)
+    return dict(zip(EQX_STAT_NAMES, (int(x) for x in out)))
 
 
 def set_ksw_routing(on=-1, rows4=-1, rows8=-1):
@@ -747,6 +804,7 @@ MM_F_AVA = MM_F_ALL_CHAINS | MM_F_NO_DIAG | MM_F_NO_DUAL | MM_F_NO_LJOIN
 # --heap-sort=yes (src/main.c:261-262): the seeds of a query merged through a binary heap (collect_seed_hits_heap, src/map.c:156-220) instead of collected and
 # radix-sorted; the two orders differ where two anchors share x. Served by the seeding and window operations and by the mapper
 MM_F_HEAP_SORT = 0x400000
+MM_F_EQX = 0x4000000          # --eqx: M ops come out as runs of = / X (mm_update_cigar_eqx, src/align.c:169-238)
 STAT_NAMES = ("super_steps", "ksw_jobs", "chain_jobs", "seed_jobs", "sketch_jobs", "dp_cells", "ksw_kernel_us", "aux_kernel_us", "read_bases")
 
 
