@@ -203,6 +203,37 @@ int wm_eqx_device_enabled(void);
 /* out6: regions deferred, rewritten on the device, rewritten on the host by the batched request while the switch was on, batched device calls, M columns those
  * calls walked, microseconds the mapper spent inside them — process-wide since the last reset. */
 void wm_eqx_stats(uint64_t *out6, int reset);
+/* The bodies of the cs:Z / MD:Z tags — write_cs_core (src/format.c:141-187) and write_MD_core (:189-218), what --cs, --cs=long and --MD print — over FINAL CIGARs
+ * as a batch, exactly as wm_cigar_cs of csrc/cigar_cs.h writes them (the specification, which the host formatter calls too; kernels: csrc/cs_kernel.h). mode:
+ * WM_CS_SHORT (0, --cs), WM_CS_LONG (1, --cs=long), WM_CS_MD (2, --MD). Only the body is written, without "\tcs:Z:" / "\tMD:Z:" and without a terminator.
+ * The codes are compared (:151, :198): N against N is a match; a byte above 4 counts and prints as N. Op codes 7 and 8 are treated like 0 (:148, :196). cs: the
+ * identical run belongs to one op and is flushed as ":<n>" / "=<BASES>" before a mismatch ("*<t><q>") and at the op's end (:152-167); "+<bases>", "-<bases>" (a
+ * zero-length I / D prints the bare sign, :169-178); "~<t0><t1><len><t[len-2]><t[len-1]>" (:181). MD: one run over the whole CIGAR, through I and N ops;
+ * "<run><T>" at a mismatch and "<run>^<BASES>" at a D, "0" included; the final run only if it is > 0 (:199-216). Jobs, operands and cigars as for
+ * wm_eqx_batch[_pos]; ops of code 0, 7 and 8 consume both operands. Job i's body lies at text_out + out[i].off and has out[i].len bytes; the bodies lie back to
+ * back in job order. out_cap: bytes text_out holds. WM_ENOMEM if it is too small: *out_used then holds the needed bytes and out[] is already filled (the rule of
+ * wm_eqx_batch). n_cigar == 0 is valid and gives len 0. WM_EINVAL, naming the job: what wm_eqx_batch[_pos] refuses about operands and n_ops; an op code outside
+ * {0, 1, 2, 3, 7, 8} (the assert of :147 / :195); in a cs mode an N op shorter than 2 (the assert of :180); a job whose bound of output bytes (3 per M column,
+ * 1 per gap base, 12 per op, 16 per N, + 11) reaches 2^31 — arithmetic inside a job is int32, offsets of jobs are 64-bit. WM_EINVAL also for a mode outside
+ * 0..2. Results do not depend on wm_extra_set_routing, whose two values route this call as well: a job's columns here are its M columns, EVERY base of an I / D
+ * op that is printed (a byte each, unlike the siblings' one column per 64 gap bases), and one per op. */
+#define WM_CS_SHORT 0
+#define WM_CS_LONG  1
+#define WM_CS_MD    2
+typedef struct { uint64_t off; uint32_t len; int32_t pad; } wm_cs_res_t;
+int wm_cs_batch(wm_ctx_t *ctx, int mode, int n_jobs, const wm_extra_job_t *jobs, const uint8_t *seqs, size_t seqs_bytes, const uint32_t *cigars, size_t n_ops,
+                char *text_out, size_t out_cap, size_t *out_used, wm_cs_res_t *out);
+int wm_cs_batch_pos(wm_ctx_t *ctx, int mode, int n_jobs, const wm_extra_pos_t *jobs, const uint32_t *cigars, size_t n_ops,
+                    char *text_out, size_t out_cap, size_t *out_used, wm_cs_res_t *out);
+/* The mapper's switch for those tags under MM_F_OUT_CS / MM_F_OUT_MD (MD wins when both are set, src/format.c:331): on = 1, the bodies of a read's printed regions
+ * are produced by one batched wm_cs_batch_pos per read once its regions are final, and travel with the read's output; 0 = the output step walks every region on
+ * the host; < 0 = what WM_CS_DEV in the environment says (read when a mapping call starts). OFF by default; without either flag it does nothing. Results do not
+ * depend on it, nor on its three siblings above. */
+void wm_set_cs_device(int on);
+int wm_cs_device_enabled(void);
+/* out6: regions deferred, served on the device, served on the host by the batched request while the switch was on, batched device calls, bytes those calls
+ * produced, microseconds the mapper spent inside them — process-wide since the last reset. */
+void wm_cs_stats(uint64_t *out6, int reset);
 
 /* diagnostics: per-phase cycle table of the stripe-pipelined wide-hull kernel; only in a library built with WM_KERNEL_DEFINES="WM_STRIPE_TIMING=1"
  * (WM_EINVAL otherwise). out16: cycles summed over wavefronts in scan / epoch set-up / cells / wait-left / bookkeeping / wait-right / publish, then rows,

@@ -72,8 +72,9 @@ struct Fiber { FiberCtx ctx; char *stack; std::function<void()> fn; bool done; S
 // finish in one small kernel, would wait for it (round 4 timeline: gpurun_out/r04f).
 // OP_EXTRA: the final scans of a read's regions (mm_update_extra's walk, ExtraReq), deferred to one request list per read when the switch is on (wm_ops.h).
 // OP_FIX: mm_fix_cigar + that scan for regions that kept their stitched CIGAR (FixReq; the switch of wm_set_fix_device), batched the same way.
+// OP_CS: the bodies of the cs:Z / MD:Z tags of a read's printed regions (CsReq; MM_F_OUT_CS / MM_F_OUT_MD with the switch of wm_set_cs_device), issued once the read's regions are final.
 // OP_EQX: mm_update_cigar_eqx over a read's final CIGARs (EqxReq; MM_F_EQX with the switch of wm_set_eqx_device), issued after the read's OP_FIX / OP_EXTRA results are in.
-enum { OP_SKETCH = 0, OP_SEED = 1, OP_CHAIN = 2, OP_KSW = 3, OP_KSW_HEAVY = 4, OP_KSW_HUGE = 5, OP_WINDOW = 6, OP_WINDOW_BIG = 7, OP_EXTRA = 8, OP_FIX = 9, OP_EQX = 10, OP_N = 11 };
+enum { OP_SKETCH = 0, OP_SEED = 1, OP_CHAIN = 2, OP_KSW = 3, OP_KSW_HEAVY = 4, OP_KSW_HUGE = 5, OP_WINDOW = 6, OP_WINDOW_BIG = 7, OP_EXTRA = 8, OP_FIX = 9, OP_EQX = 10, OP_CS = 11, OP_N = 12 };
 inline double thread_cpu_s() { timespec ts; clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 inline double wall_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -91,12 +92,13 @@ struct Hub {
 	std::mutex mu;
 	std::condition_variable cv;
 	// published requests and the fibers waiting for them (taken whole by a dispatcher)
-	std::vector<SketchReq*> q_sketch; std::vector<SeedReq*> q_seed; std::vector<ChainReq*> q_chain; std::vector<KswReq*> q_ksw, q_kswh, q_kswx; std::vector<WindowReq*> q_window, q_windowb; std::vector<ExtraReq*> q_extra; std::vector<FixReq*> q_fix; std::vector<EqxReq*> q_eqx;
+	std::vector<SketchReq*> q_sketch; std::vector<SeedReq*> q_seed; std::vector<ChainReq*> q_chain; std::vector<KswReq*> q_ksw, q_kswh, q_kswx; std::vector<WindowReq*> q_window, q_windowb; std::vector<ExtraReq*> q_extra; std::vector<FixReq*> q_fix; std::vector<EqxReq*> q_eqx; std::vector<CsReq*> q_cs;
 	bool fix_dev = false;                   // ... and mm_fix_cigar with them, to DeviceOps::fix_extra_batch (fix_device_on() when the call started)
 	bool eqx_dev = false;                   // ... and, under MM_F_EQX, the = / X rewriting after them, to DeviceOps::eqx_batch (eqx_device_on() when the call started)
+	bool cs_dev = false;                    // ... and, under MM_F_OUT_CS / MM_F_OUT_MD, the tags' bodies of a finished read to DeviceOps::cs_batch (cs_device_on() when the call started)
 	bool extra_dev = false;                 // the mapping call defers its regions' final scans to DeviceOps::extra_batch (extra_device_on() when the call started)
 	std::vector<Fiber*> waiters[OP_N];
-	int inflight = 0, inflight_op[OP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+	int inflight = 0, inflight_op[OP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 	int n_workers = 1, n_idle = 0;          // workers of the mapping call; workers asleep with nothing runnable
 	std::vector<HelpTask*> help;            // loops of running batched calls that still have chunks to hand out
 	double cpu_help = 0;                    // CPU seconds idle workers spent inside such loops
@@ -138,29 +140,29 @@ struct Hub {
 		}
 	} par;
 	std::atomic<int64_t> live{0};           // fibers alive + reads not yet admitted, over all workers: 0 = the mapping call is finished
-	uint64_t n_batches[OP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, n_reqs[OP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+	uint64_t n_batches[OP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, n_reqs[OP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 	// where the host time goes (seconds, summed over the workers): CPU time running fibers, CPU and wall time inside the batched
 	// calls per operation, wall time asleep waiting for results
-	double cpu_fiber = 0, cpu_op[OP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, wall_op[OP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, wall_idle = 0;
+	double cpu_fiber = 0, cpu_op[OP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, wall_op[OP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, wall_idle = 0;
 	double wall_fiber = 0, wall_lock = 0, wall_total = 0;     // wall time running fibers (>> cpu_fiber: the workers are being descheduled), waiting for the hub mutex, inside run()
-	size_t pending(int op) const { return op == OP_SKETCH ? q_sketch.size() : op == OP_SEED ? q_seed.size() : op == OP_CHAIN ? q_chain.size() : op == OP_KSW ? q_ksw.size() : op == OP_KSW_HEAVY ? q_kswh.size() : op == OP_KSW_HUGE ? q_kswx.size() : op == OP_WINDOW ? q_window.size() : op == OP_WINDOW_BIG ? q_windowb.size() : op == OP_EXTRA ? q_extra.size() : op == OP_FIX ? q_fix.size() : q_eqx.size(); }
+	size_t pending(int op) const { return op == OP_SKETCH ? q_sketch.size() : op == OP_SEED ? q_seed.size() : op == OP_CHAIN ? q_chain.size() : op == OP_KSW ? q_ksw.size() : op == OP_KSW_HEAVY ? q_kswh.size() : op == OP_KSW_HUGE ? q_kswx.size() : op == OP_WINDOW ? q_window.size() : op == OP_WINDOW_BIG ? q_windowb.size() : op == OP_EXTRA ? q_extra.size() : op == OP_FIX ? q_fix.size() : op == OP_EQX ? q_eqx.size() : q_cs.size(); }
 	// scheduling knobs (environment, read once per mapping call): a further concurrent batch of an operation that is already in flight is
 	// issued when at least min_more[op] requests are pending and fewer than max_op[op] batches of it are running
-	size_t min_more[OP_N] = { 4096, 4096, 4096, 24576, 2048, 64, 4096, 1024, 8192, 8192, 8192 };
-	int max_op[OP_N] = { 2, 2, 2, 3, 2, 1, 3, 2, 2, 2, 2 };
+	size_t min_more[OP_N] = { 4096, 4096, 4096, 24576, 2048, 64, 4096, 1024, 8192, 8192, 8192, 8192 };
+	int max_op[OP_N] = { 2, 2, 2, 3, 2, 1, 3, 2, 2, 2, 2, 2 };
 	// a batch is worth its fixed cost — a kernel launch lasts at least as long as its longest job, and the device runs only so many
 	// kernels at once — when it is large: an operation is issued when min_batch[op] requests are pending or the oldest has waited
 	// max_wait_ms[op], whichever comes first (0 / 0 = at once)
 	// (the huge queue: 512 jobs / 250 ms since round 5 — a launch of stripe-pipelined jobs lasts as long as its longest job whatever their number, so
 	// fewer, fuller launches: +3..9 % on config 2 together with the sixteen-wavefront routing, profiles/r05_sched.txt; before: 256 / 100 ms)
-	size_t min_batch[OP_N] = { 8192, 8192, 8192, 98304, 12288, 512, 8192, 2048, 4096, 4096, 4096 };
-	double max_wait_ms[OP_N] = { 15, 15, 15, 30, 60, 250, 15, 30, 15, 15, 15 };
-	double first_pending[OP_N] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };          // wall_s() when the queue of the operation last became non-empty
+	size_t min_batch[OP_N] = { 8192, 8192, 8192, 98304, 12288, 512, 8192, 2048, 4096, 4096, 4096, 4096 };
+	double max_wait_ms[OP_N] = { 15, 15, 15, 30, 60, 250, 15, 30, 15, 15, 15, 15 };
+	double first_pending[OP_N] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };          // wall_s() when the queue of the operation last became non-empty
 	long heavy_units = 8192;                // rows x 128-lane register pairs above which an alignment goes to the heavy queue (0 = no heavy queue)
 	long huge_units = 131072;               // ... and to the queue of the few very long ones (0 = none)
 	void read_env()
 	{
-		static const char *nm[OP_N] = { "SKETCH", "SEED", "CHAIN", "KSW", "KSWH", "KSWX", "WINDOW", "WINDOWB", "EXTRA", "FIX", "EQX" };
+		static const char *nm[OP_N] = { "SKETCH", "SEED", "CHAIN", "KSW", "KSWH", "KSWX", "WINDOW", "WINDOWB", "EXTRA", "FIX", "EQX", "CS" };
 		for (int op = 0; op < OP_N; ++op) {
 			char key[64];
 			snprintf(key, sizeof(key), "WM_%s_MIN_MORE", nm[op]); if (getenv(key)) min_more[op] = (size_t)atol(getenv(key));
@@ -320,6 +322,14 @@ public:
 		for (EqxReq &r : rs) l_eqx_.push_back(&r);
 		wait(1 << OP_EQX);
 	}
+	// ... and, when the read's regions are final, the bodies of their cs:Z / MD:Z tags (CsReq)
+	bool cs_deferred() const { return hub_->cs_dev; }
+	void cs(std::vector<CsReq> &rs)
+	{
+		if (rs.empty()) return;
+		for (CsReq &r : rs) l_cs_.push_back(&r);
+		wait(1 << OP_CS);
+	}
 	// serial work of one alignment on its wavefront: anti-diagonals x 128-lane register pairs of the band hull
 	static long ksw_units(const KswReq &r)
 	{
@@ -378,6 +388,7 @@ private:
 		if (!l_extra_.empty()) { H.q_extra.insert(H.q_extra.end(), l_extra_.begin(), l_extra_.end()); l_extra_.clear(); any = true; }
 		if (!l_fix_.empty()) { H.q_fix.insert(H.q_fix.end(), l_fix_.begin(), l_fix_.end()); l_fix_.clear(); any = true; }
 		if (!l_eqx_.empty()) { H.q_eqx.insert(H.q_eqx.end(), l_eqx_.begin(), l_eqx_.end()); l_eqx_.clear(); any = true; }
+		if (!l_cs_.empty()) { H.q_cs.insert(H.q_cs.end(), l_cs_.begin(), l_cs_.end()); l_cs_.clear(); any = true; }
 		for (int op = 0; op < OP_N; ++op)
 			if (!l_wait_[op].empty()) { H.waiters[op].insert(H.waiters[op].end(), l_wait_[op].begin(), l_wait_[op].end()); l_wait_[op].clear(); }
 		if (any) H.cv.notify_all();          // somebody idle may want to dispatch what was just published
@@ -393,7 +404,7 @@ private:
 		// nothing running anywhere and nobody able to produce more requests: whatever is pending must go now
 		const bool drain = H.inflight == 0 && H.n_idle + 1 >= H.n_workers;
 		int best = -1;
-		static const int stage_order[OP_N] = { OP_EQX, OP_FIX, OP_EXTRA, OP_KSW_HUGE, OP_KSW_HEAVY, OP_KSW, OP_WINDOW_BIG, OP_CHAIN, OP_SEED, OP_SKETCH, OP_WINDOW };
+		static const int stage_order[OP_N] = { OP_CS, OP_EQX, OP_FIX, OP_EXTRA, OP_KSW_HUGE, OP_KSW_HEAVY, OP_KSW, OP_WINDOW_BIG, OP_CHAIN, OP_SEED, OP_SKETCH, OP_WINDOW };
 		for (int oi = 0; oi < OP_N; ++oi) {                   // later stages first: finishing reads frees their memory and admits new ones
 			const int op = stage_order[oi];
 			const size_t n = H.pending(op);
@@ -411,11 +422,11 @@ private:
 		Hub &H = *hub_;
 		std::vector<Fiber*> waiters;
 		waiters.swap(H.waiters[op]);
-		std::vector<SketchReq*> a; std::vector<SeedReq*> b; std::vector<ChainReq*> c; std::vector<KswReq*> d; std::vector<WindowReq*> wq; std::vector<ExtraReq*> xq; std::vector<FixReq*> fq; std::vector<EqxReq*> eq;
+		std::vector<SketchReq*> a; std::vector<SeedReq*> b; std::vector<ChainReq*> c; std::vector<KswReq*> d; std::vector<WindowReq*> wq; std::vector<ExtraReq*> xq; std::vector<FixReq*> fq; std::vector<EqxReq*> eq; std::vector<CsReq*> cq;
 		size_t n = 0;
 		if (op == OP_SKETCH) { a.swap(H.q_sketch); n = a.size(); } else if (op == OP_SEED) { b.swap(H.q_seed); n = b.size(); }
 		else if (op == OP_CHAIN) { c.swap(H.q_chain); n = c.size(); } else if (op == OP_KSW) { d.swap(H.q_ksw); n = d.size(); } else if (op == OP_KSW_HEAVY) { d.swap(H.q_kswh); n = d.size(); }
-		else if (op == OP_KSW_HUGE) { d.swap(H.q_kswx); n = d.size(); } else if (op == OP_WINDOW) { wq.swap(H.q_window); n = wq.size(); } else if (op == OP_WINDOW_BIG) { wq.swap(H.q_windowb); n = wq.size(); } else if (op == OP_EXTRA) { xq.swap(H.q_extra); n = xq.size(); } else if (op == OP_FIX) { fq.swap(H.q_fix); n = fq.size(); } else { eq.swap(H.q_eqx); n = eq.size(); }
+		else if (op == OP_KSW_HUGE) { d.swap(H.q_kswx); n = d.size(); } else if (op == OP_WINDOW) { wq.swap(H.q_window); n = wq.size(); } else if (op == OP_WINDOW_BIG) { wq.swap(H.q_windowb); n = wq.size(); } else if (op == OP_EXTRA) { xq.swap(H.q_extra); n = xq.size(); } else if (op == OP_FIX) { fq.swap(H.q_fix); n = fq.size(); } else if (op == OP_EQX) { eq.swap(H.q_eqx); n = eq.size(); } else { cq.swap(H.q_cs); n = cq.size(); }
 		++H.inflight; ++H.inflight_op[op]; ++H.n_batches[op]; H.n_reqs[op] += n;
 		lk.unlock();
 		static const bool trace = getenv("WM_TRACE") != 0;
@@ -431,6 +442,7 @@ private:
 			else if (op == OP_EXTRA) { if (!xq.empty()) H.ops->extra_batch(xq[0]->sc, xq); }      // (one score per mapping call)
 			else if (op == OP_FIX) { if (!fq.empty()) H.ops->fix_extra_batch(fq[0]->sc, fq); }
 			else if (op == OP_EQX) { if (!eq.empty()) H.ops->eqx_batch(eq); }
+			else if (op == OP_CS) { if (!cq.empty()) H.ops->cs_batch(cq); }
 			else if (H.splice) H.ops->exts2_batch(H.sc, H.noncan, H.junc_bonus, d);
 			else H.ops->ksw_batch(H.sc, d);
 		} catch (const std::exception &e) {          // the waiters below are released in any case (their requests keep their zero-initialised results)
@@ -438,7 +450,7 @@ private:
 		} catch (...) {
 			note_internal_error("exception in a batched device call", __FILE__, __LINE__);
 		}
-		if (trace) fprintf(stderr, "[batch] worker %2d %s n=%zu %.1f ms\n", rank_, op == OP_SKETCH ? "sketch" : op == OP_SEED ? "seed" : op == OP_CHAIN ? "chain" : op == OP_KSW ? "ksw" : op == OP_KSW_HEAVY ? "ksw-heavy" : op == OP_KSW_HUGE ? "ksw-huge" : op == OP_WINDOW_BIG ? "window-big" : op == OP_EXTRA ? "extra" : op == OP_FIX ? "fix" : op == OP_EQX ? "eqx" : "window", n,
+		if (trace) fprintf(stderr, "[batch] worker %2d %s n=%zu %.1f ms\n", rank_, op == OP_SKETCH ? "sketch" : op == OP_SEED ? "seed" : op == OP_CHAIN ? "chain" : op == OP_KSW ? "ksw" : op == OP_KSW_HEAVY ? "ksw-heavy" : op == OP_KSW_HUGE ? "ksw-huge" : op == OP_WINDOW_BIG ? "window-big" : op == OP_EXTRA ? "extra" : op == OP_FIX ? "fix" : op == OP_EQX ? "eqx" : op == OP_CS ? "cs" : "window", n,
 		                   std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
 		tl_par_hook() = prev_hook;
 		const double dc = thread_cpu_s() - c0, dw = wall_s() - w0;
@@ -458,7 +470,7 @@ private:
 	std::vector<Fiber*> pool_;
 	std::vector<char*> slabs_; int slab_left_ = 0;
 	std::vector<Fiber*> inbox_;             // fibers whose results arrived (filled by dispatchers under the hub mutex)
-	std::vector<SketchReq*> l_sketch_; std::vector<SeedReq*> l_seed_; std::vector<ChainReq*> l_chain_; std::vector<KswReq*> l_ksw_, l_kswh_, l_kswx_; std::vector<WindowReq*> l_window_, l_windowb_; std::vector<ExtraReq*> l_extra_; std::vector<FixReq*> l_fix_; std::vector<EqxReq*> l_eqx_;
+	std::vector<SketchReq*> l_sketch_; std::vector<SeedReq*> l_seed_; std::vector<ChainReq*> l_chain_; std::vector<KswReq*> l_ksw_, l_kswh_, l_kswx_; std::vector<WindowReq*> l_window_, l_windowb_; std::vector<ExtraReq*> l_extra_; std::vector<FixReq*> l_fix_; std::vector<EqxReq*> l_eqx_; std::vector<CsReq*> l_cs_;
 	std::vector<Fiber*> l_wait_[OP_N];
 };
 

@@ -1,4 +1,5 @@
 #include "wm_format.h"
+#include "../cigar_cs.h"
 #include <stdio.h>
 namespace wm {
 
@@ -58,69 +59,19 @@ static void write_tags(std::string &s, const Reg &r)
 	if (r.split) { s += "\tzd:i:"; put_int(s, r.split); }
 }
 
-// cs:Z / MD:Z tags (write_cs_or_MD, src/format.c:140-231): walk the CIGAR over the aligned target / query codes
-static void write_cs_or_md(std::string &s, const Index &idx, const ReadIn &t, const Reg &r, int64_t flag)
+// cs:Z / MD:Z tags (write_cs_or_MD, src/format.c:220-243): the prefix here; the operand preparation and the walk are cs_body_host (host/wm_ops.cpp) and wm_cigar_cs
+// (csrc/cigar_cs.h: one loop for the host and as the device's specification). MD wins when both flags are set (:331). `body`: what a batched request already
+// produced for this region (ReadOut::cs, the switch of wm_set_cs_device), or 0
+static void write_cs_or_md(std::string &s, const Index &idx, const ReadIn &t, const Reg &r, int64_t flag, const std::string *body)
 {
 	if (!r.has_p) return;
-	const int ql = r.qe - r.qs, tl = r.re - r.rs;
-	std::vector<uint8_t> tseq(tl > 0 ? tl : 1), qseq(ql > 0 ? ql : 1);
-	if (tl > 0) idx.getseq(r.rid, r.rs, r.re, tseq.data());
-	for (int i = r.qs; i < r.qe; ++i) {
-		const uint8_t c = nt4_table[(uint8_t)t.seq[i]];
-		if (!r.rev) qseq[i - r.qs] = c;
-		else qseq[r.qe - i - 1] = c >= 4 ? 4 : 3 - c;
-	}
-	static const char *lower = "acgtn", *upper = "ACGTN";
-	int q_off = 0, t_off = 0;
-	if (flag & F_OUT_MD) {
-		s += "\tMD:Z:";
-		int run = 0;
-		for (uint32_t c : r.cigar) {
-			const int op = c & 0xf, len = (int)(c >> 4);
-			if (op == 0 || op == 7 || op == 8) {
-				for (int j = 0; j < len; ++j) {
-					if (qseq[q_off + j] != tseq[t_off + j]) { put_int(s, run); s += upper[tseq[t_off + j]]; run = 0; }
-					else ++run;
-				}
-				q_off += len; t_off += len;
-			} else if (op == 1) q_off += len;
-			else if (op == 2) {
-				put_int(s, run); s += '^';
-				for (int j = 0; j < len; ++j) s += upper[tseq[t_off + j]];
-				run = 0; t_off += len;
-			} else if (op == 3) t_off += len;
-		}
-		if (run > 0) put_int(s, run);
-		return;
-	}
-	const bool long_form = (flag & F_OUT_CS_LONG) != 0;
-	s += "\tcs:Z:";
-	for (uint32_t c : r.cigar) {
-		const int op = c & 0xf, len = (int)(c >> 4);
-		if (op == 0 || op == 7 || op == 8) {
-			int run = 0;
-			auto flush = [&](int end) {                                    // identical stretch ending before position `end`
-				if (run == 0) return;
-				if (long_form) { s += '='; for (int j = end - run; j < end; ++j) s += upper[qseq[q_off + j]]; }
-				else { s += ':'; put_int(s, run); }
-				run = 0;
-			};
-			for (int j = 0; j < len; ++j) {
-				if (qseq[q_off + j] != tseq[t_off + j]) { flush(j); s += '*'; s += lower[tseq[t_off + j]]; s += lower[qseq[q_off + j]]; }
-				else ++run;
-			}
-			flush(len);
-			q_off += len; t_off += len;
-		} else if (op == 1) { s += '+'; for (int j = 0; j < len; ++j) s += lower[qseq[q_off + j]]; q_off += len; }
-		else if (op == 2) { s += '-'; for (int j = 0; j < len; ++j) s += lower[tseq[t_off + j]]; t_off += len; }
-		else {                                                             // intron (splice mode only)
-			s += '~'; s += lower[tseq[t_off]]; s += lower[tseq[t_off + 1]]; put_int(s, len); s += lower[tseq[t_off + len - 2]]; s += lower[tseq[t_off + len - 1]];
-			t_off += len;
-		}
-	}
+	const int mode = (flag & F_OUT_MD) ? WM_CS_MD : (flag & F_OUT_CS_LONG) ? WM_CS_LONG : WM_CS_SHORT;
+	s += mode == WM_CS_MD ? "\tMD:Z:" : "\tcs:Z:";
+	if (body) s += *body;
+	else cs_body_host(idx, t.seq.data(), r.rid, r.rs, r.re, r.qs, r.qe, r.rev, r.cigar, mode, s);
 }
 
-static void write_paf(std::string &s, const Index &idx, const ReadIn &t, const Reg *r, int64_t flag, int rep_len)
+static void write_paf(std::string &s, const Index &idx, const ReadIn &t, const Reg *r, int64_t flag, int rep_len, const std::string *cs_body)
 {   // mm_write_paf3, src/format.c:308-334
 	const int l_seq = (int)t.seq.size();
 	if (r == 0) {
@@ -139,7 +90,7 @@ static void write_paf(std::string &s, const Index &idx, const ReadIn &t, const R
 		s.reserve(s.size() + r->cigar.size() * 4 + 64);
 		for (uint32_t c : r->cigar) { put_int(s, c >> 4); s += "MIDNSHP=XB"[c & 0xf]; }
 	}
-	if (r->has_p && (flag & (F_OUT_CS | F_OUT_MD))) write_cs_or_md(s, idx, t, *r, flag);
+	if (r->has_p && (flag & (F_OUT_CS | F_OUT_MD))) write_cs_or_md(s, idx, t, *r, flag, cs_body);
 	if ((flag & F_COPY_COMMENT) && !t.comment.empty()) { s += '\t'; s += t.comment; }
 }
 
@@ -163,7 +114,7 @@ static void put_seq(std::string &s, const char *seq, int l, bool rev, bool comp)
 	}
 }
 
-static void write_sam(std::string &s, const Index &idx, const ReadIn &t, const std::vector<Reg> &regs, int reg_idx, int64_t flag_opt, int rep_len)
+static void write_sam(std::string &s, const Index &idx, const ReadIn &t, const std::vector<Reg> &regs, int reg_idx, int64_t flag_opt, int rep_len, const std::string *cs_body)
 {   // mm_write_sam3 for one segment, src/format.c:391-548
 	const int l_seq = (int)t.seq.size(), n_regs = (int)regs.size();
 	const Reg *r = reg_idx >= 0 && reg_idx < n_regs ? &regs[reg_idx] : 0;
@@ -236,7 +187,7 @@ static void write_sam(std::string &s, const Index &idx, const ReadIn &t, const s
 				}
 			}
 		}
-		if (r->has_p && (flag_opt & (F_OUT_CS | F_OUT_MD))) write_cs_or_md(s, idx, t, *r, flag_opt);
+		if (r->has_p && (flag_opt & (F_OUT_CS | F_OUT_MD))) write_cs_or_md(s, idx, t, *r, flag_opt, cs_body);
 		if (cigar_in_tag) {
 			const uint32_t clip0 = r->rev ? l_seq - r->qe : r->qs, clip1 = r->rev ? r->qs : l_seq - r->qe;
 			const int cc = (flag & 0x800) && !(flag_opt & F_SOFTCLIP) ? 5 : 4;
@@ -257,13 +208,14 @@ void write_read(std::string &s, const Index &idx, const ReadIn &rd, const ReadOu
 		for (int j = 0; j < n; ++j) {
 			const Reg &r = out.regs[j];
 			if ((flag & F_NO_PRINT_2ND) && r.id != r.parent) continue;
-			if (flag & F_OUT_SAM) write_sam(s, idx, rd, out.regs, j, flag, out.rep_len);
-			else write_paf(s, idx, rd, &r, flag, out.rep_len);
+			const std::string *body = (size_t)j < out.cs_has.size() && out.cs_has[j] ? &out.cs[j] : 0;      // (a batched request produced it: wm_set_cs_device)
+			if (flag & F_OUT_SAM) write_sam(s, idx, rd, out.regs, j, flag, out.rep_len, body);
+			else write_paf(s, idx, rd, &r, flag, out.rep_len, body);
 			s += '\n';
 		}
 	} else if ((flag & F_PAF_NO_HIT) || ((flag & F_OUT_SAM) && !(flag & F_SAM_HIT_ONLY))) {
-		if (flag & F_OUT_SAM) write_sam(s, idx, rd, out.regs, -1, flag, out.rep_len);
-		else write_paf(s, idx, rd, 0, flag, out.rep_len);
+		if (flag & F_OUT_SAM) write_sam(s, idx, rd, out.regs, -1, flag, out.rep_len, 0);
+		else write_paf(s, idx, rd, 0, flag, out.rep_len, 0);
 		s += '\n';
 	}
 }

@@ -159,6 +159,32 @@ void stage2(Scheduler &sch, const Index &idx, const MapOpt &opt, ReadTask &T)
 	T.out->frag_gap = frag_gap;
 }
 
+// With the switch of wm_set_cs_device on and MM_F_OUT_CS / MM_F_OUT_MD set: the read's regions are final (filtered, selected, mapq set), so the bodies of the tags of
+// those that will be printed — a CIGAR, and not a secondary under MM_F_NO_PRINT_2ND (the output step, src/map.c:1189-1207) — go out as ONE batched request, and the
+// fiber waits for it before the read is handed on. MD wins when both flags are set (src/format.c:331).
+void cs_bodies(Scheduler &sch, const Index &idx, const MapOpt &opt, ReadTask &T)
+{
+	if (!(opt.flag & (F_OUT_CS | F_OUT_MD)) || !sch.cs_deferred()) return;
+	ReadOut &O = *T.out;
+	const size_t n = O.regs.size();
+	const int mode = (opt.flag & F_OUT_MD) ? 2 : (opt.flag & F_OUT_CS_LONG) ? 1 : 0;          // WM_CS_MD / WM_CS_LONG / WM_CS_SHORT
+	std::vector<CsReq> reqs;
+	reqs.reserve(n);
+	O.cs.assign(n, std::string()); O.cs_has.assign(n, 0);
+	for (size_t j = 0; j < n; ++j) {
+		const Reg &r = O.regs[j];
+		if (!r.has_p || ((opt.flag & F_NO_PRINT_2ND) && r.id != r.parent)) continue;
+		reqs.emplace_back();
+		CsReq &x = reqs.back();
+		x.idx = &idx; x.seq = T.in->seq.data(); x.rid = r.rid; x.rs = r.rs; x.re = r.re; x.qs = r.qs; x.qe = r.qe; x.rev = r.rev;
+		x.qwin_off = T.dev_off; x.qwin_len = T.qlen; x.q_pos = r.rev ? 2 * T.qlen - r.qe : r.qs;
+		x.cigar = &r.cigar; x.mode = mode; x.body = &O.cs[j];
+		O.cs_has[j] = 1;
+	}
+	cs_stats().deferred += reqs.size();
+	sch.cs(reqs);
+}
+
 } // namespace
 
 namespace {
@@ -178,6 +204,7 @@ bool spawn_read(Scheduler &sch, const Index &idx, const MapOpt &opt, const MapOp
 	const Index *ip = &idx; const MapOpt *op = &opt, *o2p = &o2;
 	auto finish = [sp, ip, op, tp, on_done]() {
 		stage2(*sp, *ip, *op, *tp);
+		cs_bodies(*sp, *ip, *op, *tp);
 		// the read is done: drop its scratch (the window keeps thousands of reads in flight)
 		std::vector<std::vector<m128>>().swap(tp->collect); std::vector<uint8_t>().swap(tp->mapped);
 		on_done();
@@ -242,6 +269,7 @@ void map_batch(const Index &idx, const MapOpt &opt, DeviceOps *ops, const std::v
 	Hub hub(ops, sc, idx.w, idx.k);
 	hub.extra_dev = extra_device_on();          // (read when the mapping call starts: wm_set_extra_device / WM_EXTRA_DEV)
 	hub.fix_dev = fix_device_on();              // (... wm_set_fix_device / WM_FIX_DEV)
+	hub.cs_dev = cs_device_on();                // (... wm_set_cs_device / WM_CS_DEV; it only matters under MM_F_OUT_CS / MM_F_OUT_MD)
 	hub.eqx_dev = eqx_device_on();              // (... wm_set_eqx_device / WM_EQX_DEV; it only matters under MM_F_EQX)
 	hub.n_workers = T;
 	hub.max_sw_mat = opt.max_sw_mat;

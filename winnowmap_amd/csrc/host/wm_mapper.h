@@ -12,6 +12,9 @@ namespace wm {
 struct ReadIn { std::string name, seq, qual, comment; };        // mm_bseq1_t, src/bseq.h
 struct ReadOut {
 	std::vector<Reg> regs; int rep_len = 0, frag_gap = 0;
+	// the bodies of the regions' cs:Z / MD:Z tags where a batched request produced them (the switch of wm_set_cs_device): parallel to regs, or empty; cs_has[j] says
+	// whether cs[j] holds region j's body — the output step walks the region itself otherwise
+	std::vector<std::string> cs; std::vector<uint8_t> cs_has;
 	// the reference ASSIGNS rep_len before mm_set_mapq reads it (src/map.c:933) only where it re-collects seeds for the whole read: the rescan of the
 	// stretches stage 1 left unmapped (:808-813) and the fallback (:859-861). On the pure-MCAS path (collected anchors cover the read) its rep_len is an
 	// uninitialised stack word (:281) and MAPQ / rl:i are not reproducible by the reference itself; there this flag is false and we use 0.

@@ -4,6 +4,8 @@
 #include "wm_sdust.h"
 #include "../cigar_fix.h"
 #include "../cigar_eqx.h"
+#include "../cigar_cs.h"
+#include "wm_index.h"
 
 namespace wm {
 
@@ -167,6 +169,55 @@ void DeviceOps::eqx_batch(std::vector<EqxReq*> &reqs)
 	eqx_stats().on_host += reqs.size();
 }
 
+// ---- the cs:Z / MD:Z bodies: the host form, and the deferred, batched operation ---------------------------------------------------------------------
+void cs_body_host(const Index &idx, const char *seq, int32_t rid, int32_t rs, int32_t re, int32_t qs, int32_t qe, bool rev, const std::vector<uint32_t> &cigar, int mode, std::string &out)
+{   // write_cs_or_MD, src/format.c:220-243
+	const int ql = qe - qs, tl = re - rs;
+	std::vector<uint8_t> tseq(tl > 0 ? tl : 1), qseq(ql > 0 ? ql : 1);
+	if (tl > 0) idx.getseq(rid, rs, re, tseq.data());
+	for (int i = qs; i < qe; ++i) {
+		const uint8_t c = nt4_table[(uint8_t)seq[i]];
+		if (!rev) qseq[i - qs] = c;
+		else qseq[qe - i - 1] = c >= 4 ? 4 : 3 - c;
+	}
+	const size_t at = out.size();
+	out.resize(at + (size_t)wm_cigar_cs_bound(cigar.data(), (int)cigar.size()));
+	const int64_t n = wm_cigar_cs(mode, cigar.data(), (int)cigar.size(), qseq.data(), tseq.data(), &out[at]);
+	WM_INVARIANT(n >= 0);                       // (the asserts of src/format.c:147, :180, :195)
+	out.resize(at + (size_t)(n > 0 ? n : 0));
+}
+static std::atomic<int> g_cs_dev(-1);             // -1: the environment decides (WM_CS_DEV), read whenever a mapping call starts
+bool cs_device_on()
+{
+	const int v = g_cs_dev.load(std::memory_order_relaxed);
+	if (v >= 0) return v != 0;
+	const char *e = getenv("WM_CS_DEV");
+	return e && atoi(e) != 0;
+}
+CsStats &cs_stats() { static CsStats s; return s; }
+// WM_EXTRA_REPORT=1: this account too
+static struct CsReport {
+	~CsReport()
+	{
+		CsStats &s = cs_stats();
+		if (!getenv("WM_EXTRA_REPORT") || !s.deferred.load()) return;
+		fprintf(stderr, "[wm] cs: %llu regions deferred, %llu served on the device, %llu on the host, %llu batched calls, %llu bytes, %llu us inside the calls\n",
+		        (unsigned long long)s.deferred.load(), (unsigned long long)s.on_device.load(), (unsigned long long)s.on_host.load(), (unsigned long long)s.calls.load(),
+		        (unsigned long long)s.bytes.load(), (unsigned long long)s.us.load());
+	}
+} g_cs_report;
+
+void DeviceOps::cs_batch(std::vector<CsReq*> &reqs)
+{
+	WM_SITE("cs.host");
+	parallel_for(1, reqs.size(), [&](size_t i) {
+		CsReq &r = *reqs[i];
+		r.body->clear();
+		cs_body_host(*r.idx, r.seq, r.rid, r.rs, r.re, r.qs, r.qe, r.rev, *r.cigar, r.mode, *r.body);
+	});
+	cs_stats().on_host += reqs.size();
+}
+
 } // namespace wm
 
 extern "C" {
@@ -177,6 +228,14 @@ void wm_fix_stats(uint64_t *out7, int reset)
 	wm::FixStats &s = wm::fix_stats();
 	std::atomic<uint64_t> *f[7] = { &s.deferred, &s.on_device, &s.on_host, &s.early, &s.calls, &s.us, &s.cols };
 	for (int i = 0; i < 7; ++i) { if (out7) out7[i] = f[i]->load(); if (reset) f[i]->store(0); }
+}
+void wm_set_cs_device(int on) { wm::g_cs_dev = on < 0 ? -1 : on ? 1 : 0; }
+int wm_cs_device_enabled(void) { return wm::cs_device_on() ? 1 : 0; }
+void wm_cs_stats(uint64_t *out6, int reset)
+{
+	wm::CsStats &s = wm::cs_stats();
+	std::atomic<uint64_t> *f[6] = { &s.deferred, &s.on_device, &s.on_host, &s.calls, &s.bytes, &s.us };
+	for (int i = 0; i < 6; ++i) { if (out6) out6[i] = f[i]->load(); if (reset) f[i]->store(0); }
 }
 void wm_set_eqx_device(int on) { wm::g_eqx_dev = on < 0 ? -1 : on ? 1 : 0; }
 int wm_eqx_device_enabled(void) { return wm::eqx_device_on() ? 1 : 0; }

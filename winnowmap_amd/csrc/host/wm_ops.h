@@ -6,6 +6,8 @@
 #include "wm_core.h"
 #include "../cigar_walk.h"
 #include <atomic>
+#include <string>
+#include <vector>
 
 namespace wm {
 
@@ -117,6 +119,20 @@ struct EqxReq {                    // mm_update_cigar_eqx (src/align.c:169-238) 
 	bool in_place = false;                                 // out: the branch of src/align.c:195-201 ran
 	bool resident() const { return qwin_off >= 0 && rid >= 0; }
 };
+struct Index;
+struct CsReq {                     // the body of a region's cs:Z / MD:Z tag (write_cs_core / write_MD_core, src/format.c:141-218), produced when the read's regions are final (the switch of wm_set_cs_device)
+	// the host form prepares its operands as write_cs_or_MD does (:220-243): the region's target through mm_idx_getseq, its query strand from the read's characters
+	const Index *idx = 0; const char *seq = 0;            // the index; the read as it came in
+	int32_t rid = -1, rs = 0, re = 0, qs = 0, qe = 0; bool rev = false;
+	// the device form reads the resident read (two-strand space: q_pos = qs, or 2 * qwin_len - qe on the reverse strand) and the uploaded reference from rs on
+	int64_t qwin_off = -1; int32_t qwin_len = 0, q_pos = 0;
+	const std::vector<uint32_t> *cigar = 0;                // the region's final CIGAR
+	int mode = 0;                                          // WM_CS_SHORT / WM_CS_LONG / WM_CS_MD (csrc/cigar_cs.h)
+	std::string *body = 0;                                 // out: the tag's body, without its "\tcs:Z:" / "\tMD:Z:"
+	bool resident() const { return qwin_off >= 0 && rid >= 0; }
+};
+// the body of one region's tag on the host: the operand preparation of write_cs_or_MD (src/format.c:220-243), then wm_cigar_cs (csrc/cigar_cs.h); appended to `out`
+void cs_body_host(const Index &idx, const char *seq, int32_t rid, int32_t rs, int32_t re, int32_t qs, int32_t qe, bool rev, const std::vector<uint32_t> &cigar, int mode, std::string &out);
 // mm_update_cigar_eqx on a vector (csrc/cigar_eqx.h); returns 1 if the in-place branch ran
 int eqx_host(std::vector<uint32_t> &cigar, const uint8_t *qseq, const uint8_t *tseq);
 // wm_extra_walk (csrc/cigar_walk.h), 16 bases per step where the build has SSE2 and match > 0 (host/wm_align.cpp)
@@ -139,6 +155,12 @@ FixStats &fix_stats();
 bool eqx_device_on();
 struct EqxStats { std::atomic<uint64_t> deferred{0}, on_device{0}, on_host{0}, calls{0}, cols{0}, us{0}; };
 EqxStats &eqx_stats();
+
+// The switch for the cs:Z / MD:Z bodies under MM_F_OUT_CS / MM_F_OUT_MD (wm_set_cs_device / WM_CS_DEV; off by default) and its account (wm_cs_stats): regions deferred,
+// served on the device, served on the host by the batched request, batched device calls, bytes they produced, microseconds inside them.
+bool cs_device_on();
+struct CsStats { std::atomic<uint64_t> deferred{0}, on_device{0}, on_host{0}, calls{0}, bytes{0}, us{0}; };
+CsStats &cs_stats();
 
 // The batch calls are synchronous (they return when the results are in the requests) and must be callable from several threads at
 // once: the hub (wm_fiber.h) keeps up to max_inflight() of them running concurrently.
@@ -169,6 +191,9 @@ struct DeviceOps {
 	// the deferred = / X rewriting of final CIGARs (MM_F_EQX with the switch above). The default runs the specification (csrc/cigar_eqx.h); the product's GpuOps
 	// overrides it with wm_eqx_batch_pos when every request is resident.
 	virtual void eqx_batch(std::vector<EqxReq*> &reqs);
+	// the bodies of the cs:Z / MD:Z tags of finished reads (MM_F_OUT_CS / MM_F_OUT_MD with the switch above). The default runs the specification (csrc/cigar_cs.h) on
+	// operands prepared as the output step prepares them; the product's GpuOps overrides it with wm_cs_batch_pos when every request is resident and none would be refused.
+	virtual void cs_batch(std::vector<CsReq*> &reqs);
 	// the whole window in one call. The default composes it from the three operations above (checker-backed implementations in the
 	// test-suite); the product's GpuOps overrides it with the HBM-resident wm_window_batch.
 	virtual void window_batch(int w, int k, std::vector<WindowReq*> &reqs);

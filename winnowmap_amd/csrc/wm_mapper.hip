@@ -371,6 +371,47 @@ struct GpuOpsCtx {
 		st.on_device += (uint64_t)n; ++st.calls; st.cols += cols; st.us += (uint64_t)((now_ms() - t0) * 1e3);
 		return true;
 	}
+	// the bodies of the cs:Z / MD:Z tags (write_cs_core / write_MD_core, src/format.c:141-218) through wm_cs_batch_pos: the final CIGARs go out, text comes back. Returns
+	// false — nothing done — unless every request is resident and none would be refused (an op the reference asserts against, a bound of 2^31 bytes: the host form
+	// reports those). The first capacity is 1/8 of the requests' bound; should the call report WM_ENOMEM for the pool, it is repeated once at the size it reported.
+	bool cs_batch(std::vector<wm::CsReq*> &reqs)
+	{
+		const int n = (int)reqs.size();
+		if (!resident || n == 0) return false;
+		const int mode = reqs[0]->mode;
+		uint64_t bound = 0;
+		for (int i = 0; i < n; ++i) {
+			const wm::CsReq &r = *reqs[i];
+			if (!r.resident() || r.mode != mode || wm_cigar_cs_check(mode, r.cigar->data(), (int)r.cigar->size()) != -1) return false;
+			const int64_t b = wm_cigar_cs_bound(r.cigar->data(), (int)r.cigar->size());
+			if (b >= ((int64_t)1 << 31)) return false;
+			bound += (uint64_t)b;
+		}
+		const double t0 = now_ms();
+		std::vector<wm_extra_pos_t> jobs(n);
+		size_t tot = 0;
+		for (int i = 0; i < n; ++i) {
+			const wm::CsReq &r = *reqs[i];
+			wm_extra_pos_t &j = jobs[i];
+			j.qwin_off = r.qwin_off; j.qwin_len = r.qwin_len; j.q_pos = r.q_pos; j.rid = r.rid; j.t_pos = r.rs; j.cig_off = (uint32_t)tot; j.n_cigar = (int32_t)r.cigar->size();
+			tot += r.cigar->size();
+		}
+		if (tot >= ((size_t)1 << 31)) { error = "cs batch exceeds 2^31 CIGAR ops"; return true; }
+		UBuf<uint32_t> cig(tot + 1, c);
+		WM_SITE("cs.cigars");
+		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) { if (!reqs[i]->cigar->empty()) memcpy(cig.data() + jobs[i].cig_off, reqs[i]->cigar->data(), reqs[i]->cigar->size() * 4); });
+		std::vector<wm_cs_res_t> res(n);
+		size_t cap = (size_t)(bound / 8) + 64, used = 0;
+		std::vector<char> pool(cap);
+		int rc = wm_cs_batch_pos(c, mode, n, jobs.data(), cig.data(), tot, pool.data(), cap, &used, res.data());
+		if (rc == WM_ENOMEM && used > cap) { cap = used; pool.resize(cap); rc = wm_cs_batch_pos(c, mode, n, jobs.data(), cig.data(), tot, pool.data(), cap, &used, res.data()); }
+		if (rc) { fail("cs"); return true; }
+		WM_SITE("cs.unpack");
+		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) { reqs[i]->body->assign(pool.data() + res[i].off, (size_t)res[i].len); });
+		wm::CsStats &st = wm::cs_stats();
+		st.on_device += (uint64_t)n; ++st.calls; st.bytes += (uint64_t)used; st.us += (uint64_t)((now_ms() - t0) * 1e3);
+		return true;
+	}
 	// splice mode (src/align.c:326-327): the requests through wm_ksw_exts2_batch, in groups whose unbanded traceback matrices fit the arena
 	void exts2_batch(const wm_ksw_score_t &sc, int noncan, int junc_bonus, std::vector<wm::KswReq*> &reqs)
 	{
@@ -559,6 +600,12 @@ struct GpuOps {                          // the device contexts of a mapper, sha
 		with(e, [&](GpuOpsCtx &x) { ran = true; run_split(x, reqs, [&](std::vector<wm::EqxReq*> &part) { if (!x.eqx_batch(part)) rest.insert(rest.end(), part.begin(), part.end()); }); });
 		if (!ran) rest = reqs;
 	}
+	void cs_batch(wm::ErrorSink &e, std::vector<wm::CsReq*> &reqs, std::vector<wm::CsReq*> &rest)
+	{
+		bool ran = false;
+		with(e, [&](GpuOpsCtx &x) { ran = true; run_split(x, reqs, [&](std::vector<wm::CsReq*> &part) { if (!x.cs_batch(part)) rest.insert(rest.end(), part.begin(), part.end()); }); });
+		if (!ran) rest = reqs;
+	}
 	// collect_seed_hits takes one (max_occ, flag) per call: the mapper's requests of one mapping call all share them
 	void window_batch(wm::ErrorSink &e, std::vector<wm::WindowReq*> &reqs) { with(e, [&](GpuOpsCtx &x) { run_split(x, reqs, [&](std::vector<wm::WindowReq*> &part) { x.window_batch(part); }); }); }
 };
@@ -596,6 +643,12 @@ struct CallOps : wm::DeviceOps {
 		std::vector<wm::FixReq*> rest;
 		g.fix_extra_batch(err, sc, reqs, rest);
 		if (!rest.empty()) wm::DeviceOps::fix_extra_batch(sc, rest);       // not resident: the host specification + walk (counted by wm_fix_stats)
+	}
+	void cs_batch(std::vector<wm::CsReq*> &reqs) override
+	{
+		std::vector<wm::CsReq*> rest;
+		g.cs_batch(err, reqs, rest);
+		if (!rest.empty()) wm::DeviceOps::cs_batch(rest);                  // not resident, or the device call would refuse it: the host specification (counted by wm_cs_stats)
 	}
 	void eqx_batch(std::vector<wm::EqxReq*> &reqs) override
 	{

@@ -3,6 +3,7 @@
 //   wm_rt.hip      runtime: errors, device contexts, arena, pinned slab, process-wide defaults
 //   wm_ksw.hip     the alignment kernels' entry points, routing, batch planning / launch / fetch (ksw2: src/ksw2_extd2_sse.c, src/ksw2_exts2_sse.c)
 //   wm_extra.hip   the scan of mm_update_extra over batches of final CIGARs (src/align.c:240-286): entry points, validation, class split, launches
+//   wm_cs.hip      the bodies of the cs:Z / MD:Z tags over batches of final CIGARs (src/format.c:141-218): entry points, validation, class split, the two passes
 //   wm_eqx.hip     mm_update_cigar_eqx over batches of final CIGARs (src/align.c:169-238): entry points, validation, class split, the two passes
 //                  ... and mm_fix_cigar in front of it (src/align.c:91-167; fix_kernel.h): wm_fix_extra_batch / wm_fix_extra_batch_pos
 //   wm_index.hip   sketch / seed / chain batch operations, the index on the device, the -W counter (src/sketch.c, src/index.c, src/map.c:97-254, src/chain.c)

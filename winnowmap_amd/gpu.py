@@ -228,6 +228,38 @@ class Context:
         lib().wm_eqx_batch_pos.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
         return self._eqx(lib().wm_eqx_batch_pos, (self._h, len(jobs), jobs.ctypes.data), cigars, len(jobs), out_cap)
 
+    # ---- the bodies of the cs:Z / MD:Z tags over final CIGARs ---------------------------------------------------
+    def _cs(self, fn, head, cigars, n_jobs, out_cap):
+        cigars = np.ascontiguousarray(cigars, np.uint32)
+        assert CS_RES_DTYPE.itemsize == 16
+        if out_cap is None:          # wm_cigar_cs_bound over all ops: 3 bytes per M column, 1 per gap base, 12 per op, 16 per N, 11 per job
+            op, ln = cigars & 0xf, (cigars >> 4).astype(np.int64)
+            out_cap = int(np.where((op == 1) | (op == 2), ln + 12, np.where(op == 3, 16, 3 * ln + 12)).sum()) + 11 * n_jobs
+        pool = np.zeros(max(int(out_cap), 1), np.uint8)
+        res = np.zeros(n_jobs, CS_RES_DTYPE)
+        used = C.c_size_t(0)
+        rc = fn(*head, cigars.ctypes.data, len(cigars), pool.ctypes.data, int(out_cap), C.byref(used), res.ctypes.data)
+        if rc != 0:
+            e = WmError("libwmgpu error %d: %s" % (rc, lib().wm_last_error().decode()))
+            e.rc, e.needed, e.res = rc, used.value, res       # (WM_ENOMEM = -3: `needed` bytes, res is already filled)
+            raise e
+        return pool[:used.value], res
+
+    def cs_batch(self, mode, jobs, seqs, cigars, out_cap=None):
+        """wm_cs_batch: mode = CS_SHORT / CS_LONG / CS_MD; jobs: structured array EXTRA_JOB_DTYPE (operands as 0..4 codes inside seqs); cigars: the FINAL CIGARs.
+        Returns (text, res): res = CS_RES_DTYPE per job, job i's tag body is text[off : off + len] (uint8, no prefix, no terminator).
+        out_cap: bytes the pool holds (None = a safe bound); too small raises WmError with .rc == -3, .needed and .res set."""
+        jobs = np.ascontiguousarray(jobs, EXTRA_JOB_DTYPE)
+        seqs = np.ascontiguousarray(seqs, np.uint8)
+        lib().wm_cs_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+        return self._cs(lib().wm_cs_batch, (self._h, int(mode), len(jobs), jobs.ctypes.data, seqs.ctypes.data, seqs.nbytes), cigars, len(jobs), out_cap)
+
+    def cs_batch_pos(self, mode, jobs, cigars, out_cap=None):
+        """wm_cs_batch_pos: jobs: structured array EXTRA_POS_DTYPE (operands as positions in the resident reads, two-strand space, and the uploaded reference)"""
+        jobs = np.ascontiguousarray(jobs, EXTRA_POS_DTYPE)
+        lib().wm_cs_batch_pos.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+        return self._cs(lib().wm_cs_batch_pos, (self._h, int(mode), len(jobs), jobs.ctypes.data), cigars, len(jobs), out_cap)
+
     def seed_batch_keyed(self, mini, mini_off, n_mini, qlen, keys, max_occ, flag, out_cap):
         """wm_seed_batch_keyed: collect_seed_hits with skip_seed's name comparison (src/map.c:132-154). mini: uint64 [n_total, 2]; keys: uint32 [n, 2]
         from Index.query_keys (None = wm_seed_batch: MM_F_NO_DIAG / MM_F_NO_DUAL are ignored). Returns (anchors uint64 [out_cap, 2], out_off, n_anchors, rep_len)."""
@@ -431,6 +463,33 @@ def eqx_stats(reset=False):
     lib().wm_eqx_stats.restype = None
     lib().wm_eqx_stats(out.ctypes.data, 1 if reset else 0)
     return dict(zip(EQX_STAT_NAMES, (int(x) for x in out)))
+
+
+CS_RES_DTYPE = np.dtype([("off", np.uint64), ("len", np.uint32), ("pad", np.int32)])                                                       # wm_cs_res_t
+CS_SHORT, CS_LONG, CS_MD = 0, 1, 2                                                                                                          # WM_CS_SHORT / _LONG / _MD
+CS_STAT_NAMES = ("deferred", "on_device", "on_host", "calls", "bytes", "device_us")
+
+
+def set_cs_device(on):
+    """wm_set_cs_device: under MM_F_OUT_CS / MM_F_OUT_MD the mapper has the bodies of a read's cs:Z / MD:Z tags produced by one batched wm_cs_batch_pos per read (off
+    by default; on < 0: back to what WM_CS_DEV in the environment says). Read when a mapping call starts; results never depend on it."""
+    lib().wm_set_cs_device.argtypes = [C.c_int]
+    lib().wm_set_cs_device.restype = None
+    lib().wm_set_cs_device(int(on))
+
+
+def cs_device_enabled():
+    lib().wm_cs_device_enabled.restype = C.c_int
+    return bool(lib().wm_cs_device_enabled())
+
+
+def cs_stats(reset=False):
+    """wm_cs_stats: regions deferred / served on the device / served on the host by the batched request, batched device calls, bytes produced, microseconds"""
+    out = np.zeros(6, np.uint64)
+    lib().wm_cs_stats.argtypes = [C.c_void_p, C.c_int]
+    lib().wm_cs_stats.restype = None
+    lib().wm_cs_stats(out.ctypes.data, 1 if reset else 0)
+    return dict(zip(CS_STAT_NAMES, (int(x) for x in out)))
 
 
 def set_ksw_routing(on=-1, rows4=-1, rows8=-1):
@@ -804,6 +863,9 @@ MM_F_AVA = MM_F_ALL_CHAINS | MM_F_NO_DIAG | MM_F_NO_DUAL | MM_F_NO_LJOIN
 # --heap-sort=yes (src/main.c:261-262): the seeds of a query merged through a binary heap (collect_seed_hits_heap, src/map.c:156-220) instead of collected and
 # radix-sorted; the two orders differ where two anchors share x. Served by the seeding and window operations and by the mapper
 MM_F_HEAP_SORT = 0x400000
+MM_F_OUT_CS = 0x040           # --cs: the cs:Z tag (write_cs_core, src/format.c:141-187); with MM_F_OUT_CS_LONG (--cs=long) identical stretches are spelled out
+MM_F_OUT_CS_LONG = 0x800
+MM_F_OUT_MD = 0x1000000       # --MD: the MD:Z tag (write_MD_core, src/format.c:189-218); it wins over --cs when both are set
 MM_F_EQX = 0x4000000          # --eqx: M ops come out as runs of = / X (mm_update_cigar_eqx, src/align.c:169-238)
 STAT_NAMES = ("super_steps", "ksw_jobs", "chain_jobs", "seed_jobs", "sketch_jobs", "dp_cells", "ksw_kernel_us", "aux_kernel_us", "read_bases")
 
