@@ -15,6 +15,8 @@
 #include "../../oracle/wm_oracle.h"
 #include "../../winnowmap_amd/csrc/reads2bit.h"
 #include <fstream>
+#include <set>
+#include <stdexcept>
 
 using namespace wm;
 
@@ -517,3 +519,166 @@ void h_zdrop_walk(const uint8_t *q, const uint8_t *t, const uint32_t *cigar, int
 	out5[0] = z.max_zdrop; out5[1] = z.t0; out5[2] = z.t1; out5[3] = z.q0; out5[4] = z.q1;
 }
 } // extern "C"
+
+// ---- the batching hub on its own (host/wm_fiber.h): fibers that file one request of every kind against ops that only record what they are handed ----
+namespace {
+enum { HK_SKETCH, HK_SEED, HK_CHAIN, HK_WINDOW, HK_KSW, HK_EXTS2, HK_EXTRA, HK_FIX, HK_EQX, HK_CS, HK_N };
+struct HubFakeOps : DeviceOps {
+	std::mutex mu;
+	std::set<const void*> got[HK_N];       // every request pointer a batch call of that kind was handed
+	long dup = 0, bad_sc = 0;              // pointers handed over twice; final-pass calls that did not carry their requests' score
+	std::atomic<int> chain_throws{0};      // the next so many chain_batch calls throw before they serve anything
+	int max_inflight() const override { return 4; }
+	template <class R> void note(int kind, const std::vector<R*> &reqs) { std::lock_guard<std::mutex> lk(mu); for (R *r : reqs) if (!got[kind].insert(r).second) ++dup; }
+	void sketch_batch(int, int, std::vector<SketchReq*> &reqs) override { note(HK_SKETCH, reqs); for (SketchReq *r : reqs) r->mini.push_back(m128()); }
+	void seed_batch(std::vector<SeedReq*> &reqs) override { note(HK_SEED, reqs); for (SeedReq *r : reqs) r->rep_len = 1; }
+	void chain_batch(std::vector<ChainReq*> &reqs) override
+	{
+		note(HK_CHAIN, reqs);
+		if (chain_throws.load() > 0 && chain_throws.fetch_sub(1) > 0) throw std::runtime_error("hub selftest: chain_batch throws");
+		for (ChainReq *r : reqs) r->u.push_back(1);
+	}
+	void window_batch(int, int, std::vector<WindowReq*> &reqs) override { note(HK_WINDOW, reqs); for (WindowReq *r : reqs) r->n_anchors = 1; }
+	void ksw_batch(const wm_ksw_score_t &, std::vector<KswReq*> &reqs) override { note(HK_KSW, reqs); for (KswReq *r : reqs) r->ez.score = 1; }
+	void exts2_batch(const wm_ksw_score_t &, int, int, std::vector<KswReq*> &reqs) override { note(HK_EXTS2, reqs); for (KswReq *r : reqs) r->ez.score = 1; }
+	void extra_batch(const wm_extra_score_t &sc, std::vector<ExtraReq*> &reqs) override { note(HK_EXTRA, reqs); if (sc.match != 7) ++bad_sc; for (ExtraReq *r : reqs) r->out.blen = 1; }
+	void fix_extra_batch(const wm_extra_score_t &sc, std::vector<FixReq*> &reqs) override { note(HK_FIX, reqs); if (sc.match != 7) ++bad_sc; for (FixReq *r : reqs) r->qshift = 1; }
+	void eqx_batch(std::vector<EqxReq*> &reqs) override { note(HK_EQX, reqs); for (EqxReq *r : reqs) r->in_place = true; }
+	void cs_batch(std::vector<CsReq*> &reqs) override { note(HK_CS, reqs); for (CsReq *r : reqs) r->body->assign("x"); }
+};
+// everything one fiber files; it outlives the run, so that a request's address names it for good
+struct HubFiberReqs {
+	SketchReq sk; SeedReq sd; ChainReq ch; WindowReq wn;
+	std::vector<KswReq> ks, ks_capped, ks_none;             // normal + heavy + huge + over max_sw_mat; only one over max_sw_mat; nothing
+	std::vector<ExtraReq> ex, ex_none, fx_ex, only_ex;      // extra(); extra() of nothing; the extras beside fixes; the extras of fix_extra() without fixes
+	std::vector<FixReq> fx, fx_alone, fx_none;              // with extras; without; nothing
+	std::vector<EqxReq> eq; std::vector<CsReq> cs; std::string body[2];
+	HubFiberReqs() : ks(4), ks_capped(1), ex(2), fx_ex(1), only_ex(1), fx(2), fx_alone(1), eq(2), cs(2)
+	{
+		const int len[4] = { 100, 3000, 40000, 50000 }, w[4] = { 10, 100, 500, 500 };      // ksw_units 400, 12000, 400000 (the default thresholds: 8192 and 131072); 2.5e9 cells
+		for (int i = 0; i < 4; ++i) { ks[i].ql = ks[i].tl = len[i]; ks[i].w = w[i]; ks[i].cigar.assign(3, 1u); }
+		ks_capped[0].ql = ks_capped[0].tl = 50000; ks_capped[0].cigar.assign(3, 1u);
+		for (std::vector<ExtraReq> *v : { &ex, &fx_ex, &only_ex }) for (ExtraReq &r : *v) r.sc.match = 7;
+		for (std::vector<FixReq> *v : { &fx, &fx_alone }) for (FixReq &r : *v) r.sc.match = 7;
+		for (int i = 0; i < 2; ++i) cs[i].body = &body[i];
+	}
+};
+// the four scheduling knobs of one operation as a fresh hub holds them
+static void hub_knobs(const Hub &H, int op, double out[4])
+{
+	const OpKnobs &k = H.knob[op];
+	out[0] = (double)k.min_more; out[1] = (double)k.max_op; out[2] = (double)k.min_batch; out[3] = k.max_wait_ms;
+}
+}
+
+#define HUB_CHECK(c) do { if (!(c)) { fprintf(stderr, "[harness] hub selftest: %s fails (line %d)\n", #c, __LINE__); return -__LINE__; } } while (0)
+#define HUB_FIBER_CHECK(c) do { if (!(c)) { int z = 0; if (fiber_fail.compare_exchange_strong(z, __LINE__)) fprintf(stderr, "[harness] hub selftest, in a fiber: %s fails (line %d)\n", #c, __LINE__); } } while (0)
+extern "C" int wmh_hub_selftest(int n_threads, int n_fibers, int splice)
+{
+	const wm_ksw_score_t sc = {};
+	// the scheduling table: the defaults, and every operation's four environment variables
+	static const char *const stem[OP_N] = { "SKETCH", "SEED", "CHAIN", "KSW", "KSWH", "KSWX", "WINDOW", "WINDOWB", "EXTRA", "FIX", "EQX", "CS" };
+	static const double dflt[OP_N][4] = {      // min_more, max_op, min_batch, max_wait_ms
+		{ 4096, 2, 8192, 15 }, { 4096, 2, 8192, 15 }, { 4096, 2, 8192, 15 }, { 24576, 3, 98304, 30 }, { 2048, 2, 12288, 60 }, { 64, 1, 512, 250 },
+		{ 4096, 3, 8192, 15 }, { 1024, 2, 2048, 30 }, { 8192, 2, 4096, 15 }, { 8192, 2, 4096, 15 }, { 8192, 2, 4096, 15 }, { 8192, 2, 4096, 15 } };
+	static const char *const knob[4] = { "MIN_MORE", "MAX", "MIN_BATCH", "MAX_WAIT_MS" };
+	static const char *const set_to[4] = { "11", "5", "13", "2.5" };
+	static const double set_val[4] = { 11, 5, 13, 2.5 };
+	{
+		HubFakeOps ops;
+		Hub H(&ops, sc, 50, 15);
+		HUB_CHECK(H.max_inflight == 4);
+		for (int op = 0; op < OP_N; ++op) { double k[4]; hub_knobs(H, op, k); for (int j = 0; j < 4; ++j) HUB_CHECK(k[j] == dflt[op][j]); }
+		for (int op = 0; op < OP_N; ++op) {
+			char key[64];
+			for (int j = 0; j < 4; ++j) { snprintf(key, sizeof(key), "WM_%s_%s", stem[op], knob[j]); setenv(key, set_to[j], 1); }
+			Hub E(&ops, sc, 50, 15);
+			for (int j = 0; j < 4; ++j) { snprintf(key, sizeof(key), "WM_%s_%s", stem[op], knob[j]); unsetenv(key); }
+			for (int o = 0; o < OP_N; ++o) { double k[4]; hub_knobs(E, o, k); for (int j = 0; j < 4; ++j) HUB_CHECK(k[j] == (o == op ? set_val[j] : dflt[o][j])); }
+		}
+	}
+	const int T = n_threads < 1 ? 1 : n_threads;
+	std::atomic<int> fiber_fail{0}, finished{0};
+	auto run_team = [&](Hub &hub, ErrorSink &sink, const std::function<void(Scheduler&, int)> &body, int n) {
+		hub.n_workers = T;
+		std::vector<std::unique_ptr<Scheduler>> sch(T);
+		for (int t = 0; t < T; ++t) { sch[t].reset(new Scheduler(&hub, t)); sch[t]->hold((n - t + T - 1) / T); }      // (as map_batch: nobody sees the call finished before every worker has spawned its fibers)
+		auto work = [&](int t) {
+			ErrorSink *const prev = tl_error_sink();
+			tl_error_sink() = &sink;
+			for (int i = t; i < n; i += T) { Scheduler *s = sch[t].get(); s->spawn([&body, s, i]() { body(*s, i); }); s->release(1); }
+			sch[t]->run();
+			tl_error_sink() = prev;
+		};
+		std::vector<std::thread> th;
+		for (int t = 1; t < T; ++t) th.emplace_back(work, t);
+		work(0);
+		for (auto &x : th) x.join();
+	};
+	{   // every filing call once per fiber
+		HubFakeOps ops;
+		Hub hub(&ops, sc, 50, 15);
+		hub.splice = splice != 0;
+		hub.max_sw_mat = 2000000000;
+		std::vector<std::unique_ptr<HubFiberReqs>> reqs(n_fibers);
+		for (auto &r : reqs) r.reset(new HubFiberReqs());
+		ErrorSink sink;
+		run_team(hub, sink, [&](Scheduler &s, int i) {
+			HubFiberReqs &r = *reqs[i];
+			s.sketch(r.sk); HUB_FIBER_CHECK(r.sk.mini.size() == 1);
+			s.seed(r.sd); HUB_FIBER_CHECK(r.sd.rep_len == 1);
+			s.chain(r.ch); HUB_FIBER_CHECK(r.ch.u.size() == 1);
+			s.window(r.wn); HUB_FIBER_CHECK(r.wn.n_anchors == 1);
+			s.ksw(r.ks);                                            // three queues (one under splice), one wait; the fourth request is over --cap-sw-mat
+			for (int j = 0; j < 3; ++j) HUB_FIBER_CHECK(r.ks[j].ez.score == 1 && r.ks[j].cigar.size() == 3);
+			s.ksw(r.ks_capped); s.ksw(r.ks_none);                   // nothing to wait for
+			for (const KswReq *c : { &r.ks[3], &r.ks_capped[0] }) HUB_FIBER_CHECK(c->ez.zdropped == 1 && c->ez.score == -0x40000000 && c->cigar.empty());
+			s.extra(r.ex); s.extra(r.ex_none);
+			for (ExtraReq &e : r.ex) HUB_FIBER_CHECK(e.out.blen == 1);
+			s.fix_extra(r.fx, r.fx_ex);                             // both lists: one wait for two operations
+			for (FixReq &f : r.fx) HUB_FIBER_CHECK(f.qshift == 1);
+			HUB_FIBER_CHECK(r.fx_ex[0].out.blen == 1);
+			s.fix_extra(r.fx_none, r.only_ex); HUB_FIBER_CHECK(r.only_ex[0].out.blen == 1);
+			s.fix_extra(r.fx_alone, r.ex_none); HUB_FIBER_CHECK(r.fx_alone[0].qshift == 1);
+			s.fix_extra(r.fx_none, r.ex_none);                      // returns at once
+			s.eqx(r.eq); for (EqxReq &e : r.eq) HUB_FIBER_CHECK(e.in_place);
+			s.cs(r.cs); for (int j = 0; j < 2; ++j) HUB_FIBER_CHECK(r.body[j] == "x");
+			++finished;
+		}, n_fibers);
+		HUB_CHECK(fiber_fail.load() == 0);
+		HUB_CHECK(finished.load() == n_fibers);
+		HUB_CHECK(sink.msg.empty());
+		HUB_CHECK(ops.dup == 0 && ops.bad_sc == 0);
+		std::set<const void*> want[HK_N];
+		for (auto &p : reqs) {
+			HubFiberReqs &r = *p;
+			want[HK_SKETCH].insert(&r.sk); want[HK_SEED].insert(&r.sd); want[HK_CHAIN].insert(&r.ch); want[HK_WINDOW].insert(&r.wn);
+			for (int j = 0; j < 3; ++j) want[splice ? HK_EXTS2 : HK_KSW].insert(&r.ks[j]);
+			for (std::vector<ExtraReq> *v : { &r.ex, &r.fx_ex, &r.only_ex }) for (ExtraReq &e : *v) want[HK_EXTRA].insert(&e);
+			for (std::vector<FixReq> *v : { &r.fx, &r.fx_alone }) for (FixReq &f : *v) want[HK_FIX].insert(&f);
+			for (EqxReq &e : r.eq) want[HK_EQX].insert(&e);
+			for (CsReq &c : r.cs) want[HK_CS].insert(&c);
+		}
+		for (int k = 0; k < HK_N; ++k) HUB_CHECK(ops.got[k] == want[k]);
+		const uint64_t n = (uint64_t)n_fibers;
+		const uint64_t filed[OP_N] = { n, n, n, splice ? 3 * n : n, splice ? 0 : n, splice ? 0 : n, n, 0, 4 * n, 3 * n, 2 * n, 2 * n };
+		for (int op = 0; op < OP_N; ++op) { HUB_CHECK(hub.n_reqs[op] == filed[op]); HUB_CHECK(filed[op] ? hub.n_batches[op] >= 1 : hub.n_batches[op] == 0); }
+	}
+	{   // a batch call that throws: its waiters resume (their requests unserved), the call's sink has the message, later batches run
+		HubFakeOps ops;
+		ops.chain_throws = 1;
+		Hub hub(&ops, sc, 50, 15);
+		std::vector<ChainReq> first(n_fibers), second(n_fibers);
+		ErrorSink sink;
+		finished = 0;
+		run_team(hub, sink, [&](Scheduler &s, int i) { s.chain(first[i]); s.chain(second[i]); ++finished; }, n_fibers);
+		HUB_CHECK(finished.load() == n_fibers);
+		HUB_CHECK(sink.msg.find("chain_batch throws") != std::string::npos);
+		HUB_CHECK(ops.dup == 0 && ops.got[HK_CHAIN].size() == 2 * (size_t)n_fibers);
+		HUB_CHECK(hub.n_reqs[OP_CHAIN] == 2 * (uint64_t)n_fibers && hub.n_batches[OP_CHAIN] >= 2);
+		size_t served = 0;
+		for (int i = 0; i < n_fibers; ++i) served += first[i].u.size() + second[i].u.size();
+		HUB_CHECK(served >= 1 && served < 2 * (size_t)n_fibers);      // (the batch that threw served nobody; every other batch served its requests)
+	}
+	return 0;
+}

@@ -17,6 +17,11 @@
 // sliding window (the worker spawns a new read when one of its reads finishes), which keeps every stage of the path —
 // sketch, seed, chain, align — in demand at the same time instead of in lock-step phases.
 // Results do not depend on how requests are batched (every job is independent), so the output is deterministic.
+//
+// An OPERATION (OP_*) is one queue of requests of one type that one DeviceOps call serves. Everything about it that is data — the stem of its
+// environment variables, its trace name, its scheduling defaults, the public report slot — is its row of op_table below; the hub's queues, counters
+// and knobs are arrays indexed by OP_*. Adding one takes five steps, all in this file: the enum value, the table row, its place in stage_order
+// (Scheduler::pick_locked), a typed filing method of Scheduler (the only way into a queue) and a `case` in Scheduler::dispatch (the only way out).
 #pragma once
 #if !defined(__x86_64__)
 #include <ucontext.h>
@@ -75,6 +80,36 @@ struct Fiber { FiberCtx ctx; char *stack; std::function<void()> fn; bool done; S
 // OP_CS: the bodies of the cs:Z / MD:Z tags of a read's printed regions (CsReq; MM_F_OUT_CS / MM_F_OUT_MD with the switch of wm_set_cs_device), issued once the read's regions are final.
 // OP_EQX: mm_update_cigar_eqx over a read's final CIGARs (EqxReq; MM_F_EQX with the switch of wm_set_eqx_device), issued after the read's OP_FIX / OP_EXTRA results are in.
 enum { OP_SKETCH = 0, OP_SEED = 1, OP_CHAIN = 2, OP_KSW = 3, OP_KSW_HEAVY = 4, OP_KSW_HUGE = 5, OP_WINDOW = 6, OP_WINDOW_BIG = 7, OP_EXTRA = 8, OP_FIX = 9, OP_EQX = 10, OP_CS = 11, OP_N = 12 };
+// What the hub knows about an operation that is not code, one row per OP_*:
+//   env           stem of its scheduling variables WM_<env>_MIN_MORE / _MAX / _MIN_BATCH / _MAX_WAIT_MS (Hub::read_env);
+//   name          what a WM_TRACE line calls it;
+//   min_more, max_op    a further concurrent batch of an operation that is already in flight is issued when at least min_more requests are pending and fewer
+//                 than max_op batches of it are running;
+//   min_batch, max_wait_ms    a batch is worth its fixed cost — a kernel launch lasts at least as long as its longest job, and the device runs only so many
+//                 kernels at once — when it is large: an operation is issued when min_batch requests are pending or the oldest has waited max_wait_ms,
+//                 whichever comes first (0 / 0 = at once)
+//                 (the huge queue: 512 jobs / 250 ms since round 5 — a launch of stripe-pipelined jobs lasts as long as its longest job whatever their number, so
+//                 fewer, fuller launches: +3..9 % on config 2 together with the sixteen-wavefront routing, profiles/r05_sched.txt; before: 256 / 100 ms);
+//   slot          which of the four public report slots (MapStats::n_batches / cpu_op / wall_op) its account is folded into: the heavy alignment queues and the
+//                 deferred final passes are reported with the ksw operation, the fused window call in the first slot.
+struct OpKnobs { size_t min_more; int max_op; size_t min_batch; double max_wait_ms; };
+struct OpRow { int op; const char *env, *name; OpKnobs dflt; int slot; };
+inline constexpr OpRow op_table[OP_N] = {
+	{ OP_SKETCH,     "SKETCH",  "sketch",     {  4096, 2,  8192,  15 }, 0 },
+	{ OP_SEED,       "SEED",    "seed",       {  4096, 2,  8192,  15 }, 1 },
+	{ OP_CHAIN,      "CHAIN",   "chain",      {  4096, 2,  8192,  15 }, 2 },
+	{ OP_KSW,        "KSW",     "ksw",        { 24576, 3, 98304,  30 }, 3 },
+	{ OP_KSW_HEAVY,  "KSWH",    "ksw-heavy",  {  2048, 2, 12288,  60 }, 3 },
+	{ OP_KSW_HUGE,   "KSWX",    "ksw-huge",   {    64, 1,   512, 250 }, 3 },
+	{ OP_WINDOW,     "WINDOW",  "window",     {  4096, 3,  8192,  15 }, 0 },
+	{ OP_WINDOW_BIG, "WINDOWB", "window-big", {  1024, 2,  2048,  30 }, 0 },
+	{ OP_EXTRA,      "EXTRA",   "extra",      {  8192, 2,  4096,  15 }, 3 },
+	{ OP_FIX,        "FIX",     "fix",        {  8192, 2,  4096,  15 }, 3 },
+	{ OP_EQX,        "EQX",     "eqx",        {  8192, 2,  4096,  15 }, 3 },
+	{ OP_CS,         "CS",      "cs",         {  8192, 2,  4096,  15 }, 3 },
+};
+constexpr bool op_table_in_order(int i = 0) { return i == OP_N || (op_table[i].op == i && op_table_in_order(i + 1)); }
+static_assert(op_table_in_order(), "op_table: row i describes operation i");
 inline double thread_cpu_s() { timespec ts; clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 inline double wall_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -91,14 +126,15 @@ struct Hub {
 	int64_t max_sw_mat = 0;                 // mm_mapopt_t::max_sw_mat (--cap-sw-mat): pairs with more DP cells are not aligned (src/align.c:323-325)
 	std::mutex mu;
 	std::condition_variable cv;
-	// published requests and the fibers waiting for them (taken whole by a dispatcher)
-	std::vector<SketchReq*> q_sketch; std::vector<SeedReq*> q_seed; std::vector<ChainReq*> q_chain; std::vector<KswReq*> q_ksw, q_kswh, q_kswx; std::vector<WindowReq*> q_window, q_windowb; std::vector<ExtraReq*> q_extra; std::vector<FixReq*> q_fix; std::vector<EqxReq*> q_eqx; std::vector<CsReq*> q_cs;
+	// published requests and the fibers waiting for them (taken whole by a dispatcher). A queue holds the requests of ONE type: only the typed filing
+	// methods of Scheduler put anything in, and Scheduler::dispatch gives every operation's queue its type back
+	std::vector<void*> q[OP_N];
 	bool fix_dev = false;                   // ... and mm_fix_cigar with them, to DeviceOps::fix_extra_batch (fix_device_on() when the call started)
 	bool eqx_dev = false;                   // ... and, under MM_F_EQX, the = / X rewriting after them, to DeviceOps::eqx_batch (eqx_device_on() when the call started)
 	bool cs_dev = false;                    // ... and, under MM_F_OUT_CS / MM_F_OUT_MD, the tags' bodies of a finished read to DeviceOps::cs_batch (cs_device_on() when the call started)
 	bool extra_dev = false;                 // the mapping call defers its regions' final scans to DeviceOps::extra_batch (extra_device_on() when the call started)
 	std::vector<Fiber*> waiters[OP_N];
-	int inflight = 0, inflight_op[OP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+	int inflight = 0, inflight_op[OP_N] = {};
 	int n_workers = 1, n_idle = 0;          // workers of the mapping call; workers asleep with nothing runnable
 	std::vector<HelpTask*> help;            // loops of running batched calls that still have chunks to hand out
 	double cpu_help = 0;                    // CPU seconds idle workers spent inside such loops
@@ -140,35 +176,25 @@ struct Hub {
 		}
 	} par;
 	std::atomic<int64_t> live{0};           // fibers alive + reads not yet admitted, over all workers: 0 = the mapping call is finished
-	uint64_t n_batches[OP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, n_reqs[OP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+	uint64_t n_batches[OP_N] = {}, n_reqs[OP_N] = {};
 	// where the host time goes (seconds, summed over the workers): CPU time running fibers, CPU and wall time inside the batched
 	// calls per operation, wall time asleep waiting for results
-	double cpu_fiber = 0, cpu_op[OP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, wall_op[OP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, wall_idle = 0;
+	double cpu_fiber = 0, cpu_op[OP_N] = {}, wall_op[OP_N] = {}, wall_idle = 0;
 	double wall_fiber = 0, wall_lock = 0, wall_total = 0;     // wall time running fibers (>> cpu_fiber: the workers are being descheduled), waiting for the hub mutex, inside run()
-	size_t pending(int op) const { return op == OP_SKETCH ? q_sketch.size() : op == OP_SEED ? q_seed.size() : op == OP_CHAIN ? q_chain.size() : op == OP_KSW ? q_ksw.size() : op == OP_KSW_HEAVY ? q_kswh.size() : op == OP_KSW_HUGE ? q_kswx.size() : op == OP_WINDOW ? q_window.size() : op == OP_WINDOW_BIG ? q_windowb.size() : op == OP_EXTRA ? q_extra.size() : op == OP_FIX ? q_fix.size() : op == OP_EQX ? q_eqx.size() : q_cs.size(); }
-	// scheduling knobs (environment, read once per mapping call): a further concurrent batch of an operation that is already in flight is
-	// issued when at least min_more[op] requests are pending and fewer than max_op[op] batches of it are running
-	size_t min_more[OP_N] = { 4096, 4096, 4096, 24576, 2048, 64, 4096, 1024, 8192, 8192, 8192, 8192 };
-	int max_op[OP_N] = { 2, 2, 2, 3, 2, 1, 3, 2, 2, 2, 2, 2 };
-	// a batch is worth its fixed cost — a kernel launch lasts at least as long as its longest job, and the device runs only so many
-	// kernels at once — when it is large: an operation is issued when min_batch[op] requests are pending or the oldest has waited
-	// max_wait_ms[op], whichever comes first (0 / 0 = at once)
-	// (the huge queue: 512 jobs / 250 ms since round 5 — a launch of stripe-pipelined jobs lasts as long as its longest job whatever their number, so
-	// fewer, fuller launches: +3..9 % on config 2 together with the sixteen-wavefront routing, profiles/r05_sched.txt; before: 256 / 100 ms)
-	size_t min_batch[OP_N] = { 8192, 8192, 8192, 98304, 12288, 512, 8192, 2048, 4096, 4096, 4096, 4096 };
-	double max_wait_ms[OP_N] = { 15, 15, 15, 30, 60, 250, 15, 30, 15, 15, 15, 15 };
-	double first_pending[OP_N] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };          // wall_s() when the queue of the operation last became non-empty
+	size_t pending(int op) const { return q[op].size(); }
+	OpKnobs knob[OP_N];                     // scheduling knobs: the defaults of op_table, overridden by the environment (read once per mapping call)
+	double first_pending[OP_N] = {};        // wall_s() when the queue of the operation last became non-empty
 	long heavy_units = 8192;                // rows x 128-lane register pairs above which an alignment goes to the heavy queue (0 = no heavy queue)
 	long huge_units = 131072;               // ... and to the queue of the few very long ones (0 = none)
 	void read_env()
 	{
-		static const char *nm[OP_N] = { "SKETCH", "SEED", "CHAIN", "KSW", "KSWH", "KSWX", "WINDOW", "WINDOWB", "EXTRA", "FIX", "EQX", "CS" };
 		for (int op = 0; op < OP_N; ++op) {
+			OpKnobs &kn = knob[op] = op_table[op].dflt;
 			char key[64];
-			snprintf(key, sizeof(key), "WM_%s_MIN_MORE", nm[op]); if (getenv(key)) min_more[op] = (size_t)atol(getenv(key));
-			snprintf(key, sizeof(key), "WM_%s_MAX", nm[op]); if (getenv(key)) max_op[op] = atoi(getenv(key));
-			snprintf(key, sizeof(key), "WM_%s_MIN_BATCH", nm[op]); if (getenv(key)) min_batch[op] = (size_t)atol(getenv(key));
-			snprintf(key, sizeof(key), "WM_%s_MAX_WAIT_MS", nm[op]); if (getenv(key)) max_wait_ms[op] = atof(getenv(key));
+			snprintf(key, sizeof(key), "WM_%s_MIN_MORE", op_table[op].env); if (getenv(key)) kn.min_more = (size_t)atol(getenv(key));
+			snprintf(key, sizeof(key), "WM_%s_MAX", op_table[op].env); if (getenv(key)) kn.max_op = atoi(getenv(key));
+			snprintf(key, sizeof(key), "WM_%s_MIN_BATCH", op_table[op].env); if (getenv(key)) kn.min_batch = (size_t)atol(getenv(key));
+			snprintf(key, sizeof(key), "WM_%s_MAX_WAIT_MS", op_table[op].env); if (getenv(key)) kn.max_wait_ms = atof(getenv(key));
 		}
 		if (getenv("WM_KSW_HEAVY_UNITS")) heavy_units = atol(getenv("WM_KSW_HEAVY_UNITS"));
 		if (getenv("WM_KSW_HUGE_UNITS")) huge_units = atol(getenv("WM_KSW_HUGE_UNITS"));
@@ -267,17 +293,18 @@ public:
 	}
 
 	// ---- called from inside a fiber ----
-	void sketch(SketchReq &r) { l_sketch_.push_back(&r); wait(1 << OP_SKETCH); }
-	void seed(SeedReq &r) { l_seed_.push_back(&r); wait(1 << OP_SEED); }
-	void chain(ChainReq &r) { l_chain_.push_back(&r); wait(1 << OP_CHAIN); }
+	void sketch(SketchReq &r) { l_q_[OP_SKETCH].push_back(&r); wait(1 << OP_SKETCH); }
+	void seed(SeedReq &r) { l_q_[OP_SEED].push_back(&r); wait(1 << OP_SEED); }
+	void chain(ChainReq &r) { l_q_[OP_CHAIN].push_back(&r); wait(1 << OP_CHAIN); }
 	void window(WindowReq &r)
 	{
 		// WM_WINDOW_BIG_LEN=8192 switches the second queue on (stage-1 windows are at most maxPrefixLength long: 8 000 for map-ont). Off by default: measured
 		// neutral (0.242 vs 0.247 Gbp/s, profiles/r04g_sched_sweep.txt) — even a window call of a dozen requests takes 50-90 ms, waiting for a device context
 		static const int big_len = getenv("WM_WINDOW_BIG_LEN") ? atoi(getenv("WM_WINDOW_BIG_LEN")) : -1;
 		const bool big = big_len >= 0 && (!r.pre.empty() || r.len > big_len);
-		(big ? l_windowb_ : l_window_).push_back(&r);
-		wait(1 << (big ? OP_WINDOW_BIG : OP_WINDOW));
+		const int op = big ? OP_WINDOW_BIG : OP_WINDOW;
+		l_q_[op].push_back(&r);
+		wait(1 << op);
 	}
 	void ksw(std::vector<KswReq> &rs)
 	{
@@ -292,7 +319,7 @@ public:
 			}
 			const long un = ksw_units(r);
 			const int op = hub_->splice ? OP_KSW : xu > 0 && un > xu ? OP_KSW_HUGE : hu > 0 && un > hu ? OP_KSW_HEAVY : OP_KSW;   // (splice mode: one queue, exts2 has no band to classify by)
-			(op == OP_KSW_HUGE ? l_kswx_ : op == OP_KSW_HEAVY ? l_kswh_ : l_ksw_).push_back(&r);
+			l_q_[op].push_back(&r);
 			ops |= 1 << op;
 		}
 		if (ops) wait(ops);
@@ -302,7 +329,7 @@ public:
 	void extra(std::vector<ExtraReq> &rs)
 	{
 		if (rs.empty()) return;
-		for (ExtraReq &r : rs) l_extra_.push_back(&r);
+		for (ExtraReq &r : rs) l_q_[OP_EXTRA].push_back(&r);
 		wait(1 << OP_EXTRA);
 	}
 	// ... and of the regions whose mm_fix_cigar waits too (FixReq), together with the scan-only ones of the same read: one wait for both lists
@@ -310,8 +337,8 @@ public:
 	void fix_extra(std::vector<FixReq> &fs, std::vector<ExtraReq> &rs)
 	{
 		if (fs.empty()) { extra(rs); return; }
-		for (FixReq &r : fs) l_fix_.push_back(&r);
-		for (ExtraReq &r : rs) l_extra_.push_back(&r);
+		for (FixReq &r : fs) l_q_[OP_FIX].push_back(&r);
+		for (ExtraReq &r : rs) l_q_[OP_EXTRA].push_back(&r);
 		wait(1 << OP_FIX | (rs.empty() ? 0 : 1 << OP_EXTRA));
 	}
 	// ... and, once those results are in, the = / X rewriting of the read's final CIGARs (EqxReq)
@@ -319,7 +346,7 @@ public:
 	void eqx(std::vector<EqxReq> &rs)
 	{
 		if (rs.empty()) return;
-		for (EqxReq &r : rs) l_eqx_.push_back(&r);
+		for (EqxReq &r : rs) l_q_[OP_EQX].push_back(&r);
 		wait(1 << OP_EQX);
 	}
 	// ... and, when the read's regions are final, the bodies of their cs:Z / MD:Z tags (CsReq)
@@ -327,7 +354,7 @@ public:
 	void cs(std::vector<CsReq> &rs)
 	{
 		if (rs.empty()) return;
-		for (CsReq &r : rs) l_cs_.push_back(&r);
+		for (CsReq &r : rs) l_q_[OP_CS].push_back(&r);
 		wait(1 << OP_CS);
 	}
 	// serial work of one alignment on its wavefront: anti-diagonals x 128-lane register pairs of the band hull
@@ -377,20 +404,10 @@ private:
 		bool any = false;
 		const double now = wall_s();
 		for (int op = 0; op < OP_N; ++op) if (H.pending(op) == 0) H.first_pending[op] = now;     // (stamps queues that are about to become non-empty)
-		if (!l_sketch_.empty()) { H.q_sketch.insert(H.q_sketch.end(), l_sketch_.begin(), l_sketch_.end()); l_sketch_.clear(); any = true; }
-		if (!l_seed_.empty()) { H.q_seed.insert(H.q_seed.end(), l_seed_.begin(), l_seed_.end()); l_seed_.clear(); any = true; }
-		if (!l_chain_.empty()) { H.q_chain.insert(H.q_chain.end(), l_chain_.begin(), l_chain_.end()); l_chain_.clear(); any = true; }
-		if (!l_ksw_.empty()) { H.q_ksw.insert(H.q_ksw.end(), l_ksw_.begin(), l_ksw_.end()); l_ksw_.clear(); any = true; }
-		if (!l_kswh_.empty()) { H.q_kswh.insert(H.q_kswh.end(), l_kswh_.begin(), l_kswh_.end()); l_kswh_.clear(); any = true; }
-		if (!l_kswx_.empty()) { H.q_kswx.insert(H.q_kswx.end(), l_kswx_.begin(), l_kswx_.end()); l_kswx_.clear(); any = true; }
-		if (!l_window_.empty()) { H.q_window.insert(H.q_window.end(), l_window_.begin(), l_window_.end()); l_window_.clear(); any = true; }
-		if (!l_windowb_.empty()) { H.q_windowb.insert(H.q_windowb.end(), l_windowb_.begin(), l_windowb_.end()); l_windowb_.clear(); any = true; }
-		if (!l_extra_.empty()) { H.q_extra.insert(H.q_extra.end(), l_extra_.begin(), l_extra_.end()); l_extra_.clear(); any = true; }
-		if (!l_fix_.empty()) { H.q_fix.insert(H.q_fix.end(), l_fix_.begin(), l_fix_.end()); l_fix_.clear(); any = true; }
-		if (!l_eqx_.empty()) { H.q_eqx.insert(H.q_eqx.end(), l_eqx_.begin(), l_eqx_.end()); l_eqx_.clear(); any = true; }
-		if (!l_cs_.empty()) { H.q_cs.insert(H.q_cs.end(), l_cs_.begin(), l_cs_.end()); l_cs_.clear(); any = true; }
-		for (int op = 0; op < OP_N; ++op)
+		for (int op = 0; op < OP_N; ++op) {
+			if (!l_q_[op].empty()) { H.q[op].insert(H.q[op].end(), l_q_[op].begin(), l_q_[op].end()); l_q_[op].clear(); any = true; }
 			if (!l_wait_[op].empty()) { H.waiters[op].insert(H.waiters[op].end(), l_wait_[op].begin(), l_wait_[op].end()); l_wait_[op].clear(); }
+		}
 		if (any) H.cv.notify_all();          // somebody idle may want to dispatch what was just published
 	}
 	// which operation this idle worker should issue now (-1: none). An operation with nothing in flight goes first (keeps every stage
@@ -410,23 +427,22 @@ private:
 			const size_t n = H.pending(op);
 			if (n == 0) continue;
 			const double waited_ms = (now - H.first_pending[op]) * 1e3;
-			const bool ripe = drain || n >= H.min_batch[op] || waited_ms >= H.max_wait_ms[op];
-			if (!ripe) { const double left = (H.max_wait_ms[op] - waited_ms) * 1e-3; if (left < *wake_in_s) *wake_in_s = left; continue; }
+			const bool ripe = drain || n >= H.knob[op].min_batch || waited_ms >= H.knob[op].max_wait_ms;
+			if (!ripe) { const double left = (H.knob[op].max_wait_ms - waited_ms) * 1e-3; if (left < *wake_in_s) *wake_in_s = left; continue; }
 			if (H.inflight_op[op] == 0) return op;
-			if (n >= H.min_more[op] && H.inflight_op[op] < H.max_op[op] && best < 0) best = op;
+			if (n >= H.knob[op].min_more && H.inflight_op[op] < H.knob[op].max_op && best < 0) best = op;
 		}
 		return best;
 	}
+	template <class R> static std::vector<R*> typed(const std::vector<void*> &q) { std::vector<R*> v; v.reserve(q.size()); for (void *p : q) v.push_back(static_cast<R*>(p)); return v; }
 	void dispatch(int op, std::unique_lock<std::mutex> &lk)
 	{
 		Hub &H = *hub_;
 		std::vector<Fiber*> waiters;
 		waiters.swap(H.waiters[op]);
-		std::vector<SketchReq*> a; std::vector<SeedReq*> b; std::vector<ChainReq*> c; std::vector<KswReq*> d; std::vector<WindowReq*> wq; std::vector<ExtraReq*> xq; std::vector<FixReq*> fq; std::vector<EqxReq*> eq; std::vector<CsReq*> cq;
-		size_t n = 0;
-		if (op == OP_SKETCH) { a.swap(H.q_sketch); n = a.size(); } else if (op == OP_SEED) { b.swap(H.q_seed); n = b.size(); }
-		else if (op == OP_CHAIN) { c.swap(H.q_chain); n = c.size(); } else if (op == OP_KSW) { d.swap(H.q_ksw); n = d.size(); } else if (op == OP_KSW_HEAVY) { d.swap(H.q_kswh); n = d.size(); }
-		else if (op == OP_KSW_HUGE) { d.swap(H.q_kswx); n = d.size(); } else if (op == OP_WINDOW) { wq.swap(H.q_window); n = wq.size(); } else if (op == OP_WINDOW_BIG) { wq.swap(H.q_windowb); n = wq.size(); } else if (op == OP_EXTRA) { xq.swap(H.q_extra); n = xq.size(); } else if (op == OP_FIX) { fq.swap(H.q_fix); n = fq.size(); } else if (op == OP_EQX) { eq.swap(H.q_eqx); n = eq.size(); } else { cq.swap(H.q_cs); n = cq.size(); }
+		std::vector<void*> q;
+		q.swap(H.q[op]);
+		const size_t n = q.size();
 		++H.inflight; ++H.inflight_op[op]; ++H.n_batches[op]; H.n_reqs[op] += n;
 		lk.unlock();
 		static const bool trace = getenv("WM_TRACE") != 0;
@@ -435,22 +451,28 @@ private:
 		ParHook *const prev_hook = tl_par_hook();
 		tl_par_hook() = &H.par;
 		try {
-			if (op == OP_SKETCH) H.ops->sketch_batch(H.w, H.k, a);
-			else if (op == OP_SEED) H.ops->seed_batch(b);
-			else if (op == OP_CHAIN) H.ops->chain_batch(c);
-			else if (op == OP_WINDOW || op == OP_WINDOW_BIG) H.ops->window_batch(H.w, H.k, wq);
-			else if (op == OP_EXTRA) { if (!xq.empty()) H.ops->extra_batch(xq[0]->sc, xq); }      // (one score per mapping call)
-			else if (op == OP_FIX) { if (!fq.empty()) H.ops->fix_extra_batch(fq[0]->sc, fq); }
-			else if (op == OP_EQX) { if (!eq.empty()) H.ops->eqx_batch(eq); }
-			else if (op == OP_CS) { if (!cq.empty()) H.ops->cs_batch(cq); }
-			else if (H.splice) H.ops->exts2_batch(H.sc, H.noncan, H.junc_bonus, d);
-			else H.ops->ksw_batch(H.sc, d);
+			switch (op) {          // the queue gets its type back: what the filing method of this operation put in
+			case OP_SKETCH: { auto a = typed<SketchReq>(q); H.ops->sketch_batch(H.w, H.k, a); break; }
+			case OP_SEED: { auto b = typed<SeedReq>(q); H.ops->seed_batch(b); break; }
+			case OP_CHAIN: { auto c = typed<ChainReq>(q); H.ops->chain_batch(c); break; }
+			case OP_KSW: case OP_KSW_HEAVY: case OP_KSW_HUGE: {
+				auto d = typed<KswReq>(q);
+				if (H.splice) H.ops->exts2_batch(H.sc, H.noncan, H.junc_bonus, d);
+				else H.ops->ksw_batch(H.sc, d);
+				break;
+			}
+			case OP_WINDOW: case OP_WINDOW_BIG: { auto wq = typed<WindowReq>(q); H.ops->window_batch(H.w, H.k, wq); break; }
+			case OP_EXTRA: { auto xq = typed<ExtraReq>(q); if (!xq.empty()) H.ops->extra_batch(xq[0]->sc, xq); break; }      // (one score per mapping call)
+			case OP_FIX: { auto fq = typed<FixReq>(q); if (!fq.empty()) H.ops->fix_extra_batch(fq[0]->sc, fq); break; }
+			case OP_EQX: { auto eq = typed<EqxReq>(q); if (!eq.empty()) H.ops->eqx_batch(eq); break; }
+			case OP_CS: { auto cq = typed<CsReq>(q); if (!cq.empty()) H.ops->cs_batch(cq); break; }
+			}
 		} catch (const std::exception &e) {          // the waiters below are released in any case (their requests keep their zero-initialised results)
 			note_internal_error(e.what(), __FILE__, __LINE__);
 		} catch (...) {
 			note_internal_error("exception in a batched device call", __FILE__, __LINE__);
 		}
-		if (trace) fprintf(stderr, "[batch] worker %2d %s n=%zu %.1f ms\n", rank_, op == OP_SKETCH ? "sketch" : op == OP_SEED ? "seed" : op == OP_CHAIN ? "chain" : op == OP_KSW ? "ksw" : op == OP_KSW_HEAVY ? "ksw-heavy" : op == OP_KSW_HUGE ? "ksw-huge" : op == OP_WINDOW_BIG ? "window-big" : op == OP_EXTRA ? "extra" : op == OP_FIX ? "fix" : op == OP_EQX ? "eqx" : op == OP_CS ? "cs" : "window", n,
+		if (trace) fprintf(stderr, "[batch] worker %2d %s n=%zu %.1f ms\n", rank_, op_table[op].name, n,
 		                   std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
 		tl_par_hook() = prev_hook;
 		const double dc = thread_cpu_s() - c0, dw = wall_s() - w0;
@@ -470,7 +492,7 @@ private:
 	std::vector<Fiber*> pool_;
 	std::vector<char*> slabs_; int slab_left_ = 0;
 	std::vector<Fiber*> inbox_;             // fibers whose results arrived (filled by dispatchers under the hub mutex)
-	std::vector<SketchReq*> l_sketch_; std::vector<SeedReq*> l_seed_; std::vector<ChainReq*> l_chain_; std::vector<KswReq*> l_ksw_, l_kswh_, l_kswx_; std::vector<WindowReq*> l_window_, l_windowb_; std::vector<ExtraReq*> l_extra_; std::vector<FixReq*> l_fix_; std::vector<EqxReq*> l_eqx_; std::vector<CsReq*> l_cs_;
+	std::vector<void*> l_q_[OP_N];          // requests filed since the last publish, per operation (the types of Hub::q)
 	std::vector<Fiber*> l_wait_[OP_N];
 };
 

@@ -319,8 +319,8 @@ void map_batch(const Index &idx, const MapOpt &opt, DeviceOps *ops, const std::v
 		if (getenv("WM_TRACE")) { for (auto &e : hub.site_cpu) fprintf(stderr, "[site] %-28s %8.2f s CPU\n", e.first, e.second); }
 		stats->cpu_fiber += hub.cpu_fiber; stats->wall_idle += hub.wall_idle; stats->cpu_help += hub.cpu_help;
 		stats->wall_fiber += hub.wall_fiber; stats->wall_lock += hub.wall_lock; stats->wall_total += hub.wall_total;
-		for (int op = 0; op < OP_N; ++op) {           // (the heavy alignment queues and the deferred final scans are reported with the ksw operation, the fused window call in the first slot)
-			const int o = op == OP_WINDOW || op == OP_WINDOW_BIG ? 0 : op >= OP_KSW_HEAVY ? OP_KSW : op;
+		for (int op = 0; op < OP_N; ++op) {           // (every operation is reported in the public slot its row of op_table names)
+			const int o = op_table[op].slot;
 			stats->n_batches[o] += hub.n_batches[op]; stats->cpu_op[o] += hub.cpu_op[op]; stats->wall_op[o] += hub.wall_op[op];
 		}
 	}

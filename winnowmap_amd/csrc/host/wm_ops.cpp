@@ -58,26 +58,9 @@ void DeviceOps::window_batch(int w, int k, std::vector<WindowReq*> &reqs)
 }
 
 // ---- the scan of mm_update_extra as a deferred, batched operation ----------------------------------------------------------------------------
-static std::atomic<int> g_extra_dev(-1);          // -1: the environment decides (WM_EXTRA_DEV), read whenever a mapping call starts
-bool extra_device_on()
-{
-	const int v = g_extra_dev.load(std::memory_order_relaxed);
-	if (v >= 0) return v != 0;
-	const char *e = getenv("WM_EXTRA_DEV");
-	return e && atoi(e) != 0;
-}
+static DevSwitch g_extra_dev{"WM_EXTRA_DEV"};
+bool extra_device_on() { return g_extra_dev.on(); }
 ExtraStats &extra_stats() { static ExtraStats s; return s; }
-// WM_EXTRA_REPORT=1: the account on stderr when the library is unloaded (a front end that is not ours — the benchmark — has no other way to ask)
-static struct ExtraReport {
-	~ExtraReport()
-	{
-		ExtraStats &s = extra_stats();
-		if (!getenv("WM_EXTRA_REPORT") || !s.deferred.load()) return;
-		fprintf(stderr, "[wm] extra: %llu regions deferred, %llu walked on the device, %llu on the host, %llu batched calls, %llu columns, %llu us inside the calls\n",
-		        (unsigned long long)s.deferred.load(), (unsigned long long)s.on_device.load(), (unsigned long long)s.on_host.load(), (unsigned long long)s.calls.load(),
-		        (unsigned long long)s.cols.load(), (unsigned long long)s.us.load());
-	}
-} g_extra_report;
 
 void DeviceOps::extra_batch(const wm_extra_score_t &sc, std::vector<ExtraReq*> &reqs)
 {
@@ -91,36 +74,9 @@ void DeviceOps::extra_batch(const wm_extra_score_t &sc, std::vector<ExtraReq*> &
 }
 
 // ---- mm_fix_cigar + the scan as one deferred, batched operation -------------------------------------------------------------------------------
-static std::atomic<int> g_fix_dev(-1);            // -1: the environment decides (WM_FIX_DEV), read whenever a mapping call starts
-bool fix_device_on()
-{
-	const int v = g_fix_dev.load(std::memory_order_relaxed);
-	if (v >= 0) return v != 0;
-	const char *e = getenv("WM_FIX_DEV");
-	return e && atoi(e) != 0;
-}
+static DevSwitch g_fix_dev{"WM_FIX_DEV"};
+bool fix_device_on() { return g_fix_dev.on(); }
 FixStats &fix_stats() { static FixStats s; return s; }
-// WM_EXTRA_REPORT=1: this account too, and the one of the = / X rewriting
-static struct EqxReport {
-	~EqxReport()
-	{
-		EqxStats &s = eqx_stats();
-		if (!getenv("WM_EXTRA_REPORT") || !s.deferred.load()) return;
-		fprintf(stderr, "[wm] eqx: %llu regions deferred, %llu rewritten on the device, %llu on the host, %llu batched calls, %llu M columns, %llu us inside the calls\n",
-		        (unsigned long long)s.deferred.load(), (unsigned long long)s.on_device.load(), (unsigned long long)s.on_host.load(), (unsigned long long)s.calls.load(),
-		        (unsigned long long)s.cols.load(), (unsigned long long)s.us.load());
-	}
-} g_eqx_report;
-static struct FixReport {
-	~FixReport()
-	{
-		FixStats &s = fix_stats();
-		if (!getenv("WM_EXTRA_REPORT") || !s.deferred.load()) return;
-		fprintf(stderr, "[wm] fix: %llu regions deferred, %llu fixed on the device, %llu on the host, %llu early on the host (inversion test), %llu batched calls, %llu us inside the calls, %llu columns\n",
-		        (unsigned long long)s.deferred.load(), (unsigned long long)s.on_device.load(), (unsigned long long)s.on_host.load(), (unsigned long long)s.early.load(),
-		        (unsigned long long)s.calls.load(), (unsigned long long)s.us.load(), (unsigned long long)s.cols.load());
-	}
-} g_fix_report;
 
 void DeviceOps::fix_extra_batch(const wm_extra_score_t &sc, std::vector<FixReq*> &reqs)
 {
@@ -149,14 +105,8 @@ int eqx_host(std::vector<uint32_t> &cigar, const uint8_t *qseq, const uint8_t *t
 	cigar.swap(out);
 	return 0;
 }
-static std::atomic<int> g_eqx_dev(-1);            // -1: the environment decides (WM_EQX_DEV), read whenever a mapping call starts
-bool eqx_device_on()
-{
-	const int v = g_eqx_dev.load(std::memory_order_relaxed);
-	if (v >= 0) return v != 0;
-	const char *e = getenv("WM_EQX_DEV");
-	return e && atoi(e) != 0;
-}
+static DevSwitch g_eqx_dev{"WM_EQX_DEV"};
+bool eqx_device_on() { return g_eqx_dev.on(); }
 EqxStats &eqx_stats() { static EqxStats s; return s; }
 
 void DeviceOps::eqx_batch(std::vector<EqxReq*> &reqs)
@@ -186,26 +136,9 @@ void cs_body_host(const Index &idx, const char *seq, int32_t rid, int32_t rs, in
 	WM_INVARIANT(n >= 0);                       // (the asserts of src/format.c:147, :180, :195)
 	out.resize(at + (size_t)(n > 0 ? n : 0));
 }
-static std::atomic<int> g_cs_dev(-1);             // -1: the environment decides (WM_CS_DEV), read whenever a mapping call starts
-bool cs_device_on()
-{
-	const int v = g_cs_dev.load(std::memory_order_relaxed);
-	if (v >= 0) return v != 0;
-	const char *e = getenv("WM_CS_DEV");
-	return e && atoi(e) != 0;
-}
+static DevSwitch g_cs_dev{"WM_CS_DEV"};
+bool cs_device_on() { return g_cs_dev.on(); }
 CsStats &cs_stats() { static CsStats s; return s; }
-// WM_EXTRA_REPORT=1: this account too
-static struct CsReport {
-	~CsReport()
-	{
-		CsStats &s = cs_stats();
-		if (!getenv("WM_EXTRA_REPORT") || !s.deferred.load()) return;
-		fprintf(stderr, "[wm] cs: %llu regions deferred, %llu served on the device, %llu on the host, %llu batched calls, %llu bytes, %llu us inside the calls\n",
-		        (unsigned long long)s.deferred.load(), (unsigned long long)s.on_device.load(), (unsigned long long)s.on_host.load(), (unsigned long long)s.calls.load(),
-		        (unsigned long long)s.bytes.load(), (unsigned long long)s.us.load());
-	}
-} g_cs_report;
 
 void DeviceOps::cs_batch(std::vector<CsReq*> &reqs)
 {
@@ -218,39 +151,52 @@ void DeviceOps::cs_batch(std::vector<CsReq*> &reqs)
 	cs_stats().on_host += reqs.size();
 }
 
+// ---- the accounts of the four switches: the C entry points' copy-out, and the lines at unload --------------------------------------------------------
+typedef std::initializer_list<std::atomic<uint64_t>*> StatFields;      // an account's counters in the order its entry point documents (include/wm_gpu.h)
+static void take_stats(StatFields f, uint64_t *out, int reset)
+{
+	size_t i = 0;
+	for (std::atomic<uint64_t> *a : f) { if (out) out[i] = a->load(); if (reset) a->store(0); ++i; }
+}
+// WM_EXTRA_REPORT=1: the accounts on stderr when the library is unloaded (a front end that is not ours — the benchmark — has no other way to ask); an account
+// with nothing deferred prints nothing. Every '#' of `text` is the next counter.
+static void report_line(const char *text, StatFields f)
+{
+	if (!(*f.begin())->load()) return;
+	std::string line;
+	const std::atomic<uint64_t> *const *next = f.begin();
+	for (const char *p = text; *p; ++p) { if (*p == '#') line += std::to_string((*next++)->load()); else line += *p; }
+	fputs(line.c_str(), stderr);
+}
+static struct AccountReport {
+	~AccountReport()
+	{
+		if (!getenv("WM_EXTRA_REPORT")) return;
+		CsStats &c = cs_stats(); FixStats &f = fix_stats(); EqxStats &q = eqx_stats(); ExtraStats &x = extra_stats();
+		report_line("[wm] cs: # regions deferred, # served on the device, # on the host, # batched calls, # bytes, # us inside the calls\n",
+		            { &c.deferred, &c.on_device, &c.on_host, &c.calls, &c.bytes, &c.us });
+		report_line("[wm] fix: # regions deferred, # fixed on the device, # on the host, # early on the host (inversion test), # batched calls, # us inside the calls, # columns\n",
+		            { &f.deferred, &f.on_device, &f.on_host, &f.early, &f.calls, &f.us, &f.cols });
+		report_line("[wm] eqx: # regions deferred, # rewritten on the device, # on the host, # batched calls, # M columns, # us inside the calls\n",
+		            { &q.deferred, &q.on_device, &q.on_host, &q.calls, &q.cols, &q.us });
+		report_line("[wm] extra: # regions deferred, # walked on the device, # on the host, # batched calls, # columns, # us inside the calls\n",
+		            { &x.deferred, &x.on_device, &x.on_host, &x.calls, &x.cols, &x.us });
+	}
+} g_account_report;
+
 } // namespace wm
 
 extern "C" {
-void wm_set_fix_device(int on) { wm::g_fix_dev = on < 0 ? -1 : on ? 1 : 0; }
+void wm_set_fix_device(int on) { wm::g_fix_dev.set(on); }
 int wm_fix_device_enabled(void) { return wm::fix_device_on() ? 1 : 0; }
-void wm_fix_stats(uint64_t *out7, int reset)
-{
-	wm::FixStats &s = wm::fix_stats();
-	std::atomic<uint64_t> *f[7] = { &s.deferred, &s.on_device, &s.on_host, &s.early, &s.calls, &s.us, &s.cols };
-	for (int i = 0; i < 7; ++i) { if (out7) out7[i] = f[i]->load(); if (reset) f[i]->store(0); }
-}
-void wm_set_cs_device(int on) { wm::g_cs_dev = on < 0 ? -1 : on ? 1 : 0; }
+void wm_fix_stats(uint64_t *out7, int reset) { wm::FixStats &s = wm::fix_stats(); wm::take_stats({ &s.deferred, &s.on_device, &s.on_host, &s.early, &s.calls, &s.us, &s.cols }, out7, reset); }
+void wm_set_cs_device(int on) { wm::g_cs_dev.set(on); }
 int wm_cs_device_enabled(void) { return wm::cs_device_on() ? 1 : 0; }
-void wm_cs_stats(uint64_t *out6, int reset)
-{
-	wm::CsStats &s = wm::cs_stats();
-	std::atomic<uint64_t> *f[6] = { &s.deferred, &s.on_device, &s.on_host, &s.calls, &s.bytes, &s.us };
-	for (int i = 0; i < 6; ++i) { if (out6) out6[i] = f[i]->load(); if (reset) f[i]->store(0); }
-}
-void wm_set_eqx_device(int on) { wm::g_eqx_dev = on < 0 ? -1 : on ? 1 : 0; }
+void wm_cs_stats(uint64_t *out6, int reset) { wm::CsStats &s = wm::cs_stats(); wm::take_stats({ &s.deferred, &s.on_device, &s.on_host, &s.calls, &s.bytes, &s.us }, out6, reset); }
+void wm_set_eqx_device(int on) { wm::g_eqx_dev.set(on); }
 int wm_eqx_device_enabled(void) { return wm::eqx_device_on() ? 1 : 0; }
-void wm_eqx_stats(uint64_t *out6, int reset)
-{
-	wm::EqxStats &s = wm::eqx_stats();
-	std::atomic<uint64_t> *f[6] = { &s.deferred, &s.on_device, &s.on_host, &s.calls, &s.cols, &s.us };
-	for (int i = 0; i < 6; ++i) { if (out6) out6[i] = f[i]->load(); if (reset) f[i]->store(0); }
-}
-void wm_set_extra_device(int on) { wm::g_extra_dev = on < 0 ? -1 : on ? 1 : 0; }
+void wm_eqx_stats(uint64_t *out6, int reset) { wm::EqxStats &s = wm::eqx_stats(); wm::take_stats({ &s.deferred, &s.on_device, &s.on_host, &s.calls, &s.cols, &s.us }, out6, reset); }
+void wm_set_extra_device(int on) { wm::g_extra_dev.set(on); }
 int wm_extra_device_enabled(void) { return wm::extra_device_on() ? 1 : 0; }
-void wm_extra_stats(uint64_t *out6, int reset)
-{
-	wm::ExtraStats &s = wm::extra_stats();
-	std::atomic<uint64_t> *f[6] = { &s.deferred, &s.on_device, &s.on_host, &s.calls, &s.cols, &s.us };
-	for (int i = 0; i < 6; ++i) { if (out6) out6[i] = f[i]->load(); if (reset) f[i]->store(0); }
-}
+void wm_extra_stats(uint64_t *out6, int reset) { wm::ExtraStats &s = wm::extra_stats(); wm::take_stats({ &s.deferred, &s.on_device, &s.on_host, &s.calls, &s.cols, &s.us }, out6, reset); }
 }

@@ -6,6 +6,7 @@
 #include "wm_core.h"
 #include "../cigar_walk.h"
 #include <atomic>
+#include <stdlib.h>
 #include <string>
 #include <vector>
 
@@ -137,6 +138,20 @@ void cs_body_host(const Index &idx, const char *seq, int32_t rid, int32_t rs, in
 int eqx_host(std::vector<uint32_t> &cigar, const uint8_t *qseq, const uint8_t *tseq);
 // wm_extra_walk (csrc/cigar_walk.h), 16 bases per step where the build has SSE2 and match > 0 (host/wm_align.cpp)
 void extra_walk_host(const uint8_t *qseq, const uint8_t *tseq, const uint32_t *cigar, int n_cigar, int match, int mismatch, int ambi, int q, int e, wm_extra_t *out);
+
+// An opt-in switch of the mapper: what wm_set_X_device last said, or, while that is -1, what the variable `env` says whenever a mapping call starts.
+struct DevSwitch {
+	const char *env;
+	std::atomic<int> v{-1};
+	bool on() const
+	{
+		const int x = v.load(std::memory_order_relaxed);
+		if (x >= 0) return x != 0;
+		const char *e = getenv(env);
+		return e && atoi(e) != 0;
+	}
+	void set(int on_) { v = on_ < 0 ? -1 : on_ ? 1 : 0; }
+};
 
 // The mapper's switch for that scan (wm_set_extra_device / WM_EXTRA_DEV, include/wm_gpu.h; off by default) and its process-wide account (wm_extra_stats). They live
 // with the host mapper, so the test harness has them too.

@@ -587,23 +587,12 @@ struct GpuOps {                          // the device contexts of a mapper, sha
 		*served = false;
 		with(e, [&](GpuOpsCtx &x) { bool all = true; run_split(x, reqs, [&](std::vector<wm::ExtraReq*> &part) { all = x.extra_batch(sc, part) && all; }); *served = all; });
 	}
-	// rest: the requests of parts that were not served (not resident, or refusable); they are untouched
-	void fix_extra_batch(wm::ErrorSink &e, const wm_extra_score_t &sc, std::vector<wm::FixReq*> &reqs, std::vector<wm::FixReq*> &rest)
+	// the final-pass calls that may decline a part: call(x, part) = false leaves the part untouched, and it goes to `rest` (not resident, or refusable) — as does
+	// everything when the mapping call has failed already and nothing was issued
+	template <class R, class F> void batch_or_rest(wm::ErrorSink &e, std::vector<R*> &reqs, std::vector<R*> &rest, F call)
 	{
 		bool ran = false;
-		with(e, [&](GpuOpsCtx &x) { ran = true; run_split(x, reqs, [&](std::vector<wm::FixReq*> &part) { if (!x.fix_extra_batch(sc, part)) rest.insert(rest.end(), part.begin(), part.end()); }); });
-		if (!ran) rest = reqs;
-	}
-	void eqx_batch(wm::ErrorSink &e, std::vector<wm::EqxReq*> &reqs, std::vector<wm::EqxReq*> &rest)
-	{
-		bool ran = false;
-		with(e, [&](GpuOpsCtx &x) { ran = true; run_split(x, reqs, [&](std::vector<wm::EqxReq*> &part) { if (!x.eqx_batch(part)) rest.insert(rest.end(), part.begin(), part.end()); }); });
-		if (!ran) rest = reqs;
-	}
-	void cs_batch(wm::ErrorSink &e, std::vector<wm::CsReq*> &reqs, std::vector<wm::CsReq*> &rest)
-	{
-		bool ran = false;
-		with(e, [&](GpuOpsCtx &x) { ran = true; run_split(x, reqs, [&](std::vector<wm::CsReq*> &part) { if (!x.cs_batch(part)) rest.insert(rest.end(), part.begin(), part.end()); }); });
+		with(e, [&](GpuOpsCtx &x) { ran = true; run_split(x, reqs, [&](std::vector<R*> &part) { if (!call(x, part)) rest.insert(rest.end(), part.begin(), part.end()); }); });
 		if (!ran) rest = reqs;
 	}
 	// collect_seed_hits takes one (max_occ, flag) per call: the mapper's requests of one mapping call all share them
@@ -641,19 +630,19 @@ struct CallOps : wm::DeviceOps {
 	void fix_extra_batch(const wm_extra_score_t &sc, std::vector<wm::FixReq*> &reqs) override
 	{
 		std::vector<wm::FixReq*> rest;
-		g.fix_extra_batch(err, sc, reqs, rest);
+		g.batch_or_rest(err, reqs, rest, [&](GpuOpsCtx &x, std::vector<wm::FixReq*> &part) { return x.fix_extra_batch(sc, part); });
 		if (!rest.empty()) wm::DeviceOps::fix_extra_batch(sc, rest);       // not resident: the host specification + walk (counted by wm_fix_stats)
 	}
 	void cs_batch(std::vector<wm::CsReq*> &reqs) override
 	{
 		std::vector<wm::CsReq*> rest;
-		g.cs_batch(err, reqs, rest);
+		g.batch_or_rest(err, reqs, rest, [](GpuOpsCtx &x, std::vector<wm::CsReq*> &part) { return x.cs_batch(part); });
 		if (!rest.empty()) wm::DeviceOps::cs_batch(rest);                  // not resident, or the device call would refuse it: the host specification (counted by wm_cs_stats)
 	}
 	void eqx_batch(std::vector<wm::EqxReq*> &reqs) override
 	{
 		std::vector<wm::EqxReq*> rest;
-		g.eqx_batch(err, reqs, rest);
+		g.batch_or_rest(err, reqs, rest, [](GpuOpsCtx &x, std::vector<wm::EqxReq*> &part) { return x.eqx_batch(part); });
 		if (!rest.empty()) wm::DeviceOps::eqx_batch(rest);                 // not resident: the host specification (counted by wm_eqx_stats)
 	}
 };

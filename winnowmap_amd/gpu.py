@@ -372,6 +372,33 @@ class KswDevBatch:
             self._h = None
 
 
+def _device_switch(stem, stat_names, set_doc, stats_doc):
+    """the three wrappers of one opt-in switch of the mapper: wm_set_<stem>_device, wm_<stem>_device_enabled and wm_<stem>_stats (one counter per name)"""
+    def set_device(on):
+        f = getattr(lib(), "wm_set_%s_device" % stem)
+        f.argtypes = [C.c_int]
+        f.restype = None
+        f(int(on))
+
+    def device_enabled():
+        f = getattr(lib(), "wm_%s_device_enabled" % stem)
+        f.restype = C.c_int
+        return bool(f())
+
+    def stats(reset=False):
+        out = np.zeros(len(stat_names), np.uint64)
+        f = getattr(lib(), "wm_%s_stats" % stem)
+        f.argtypes = [C.c_void_p, C.c_int]
+        f.restype = None
+        f(out.ctypes.data, 1 if reset else 0)
+        return dict(zip(stat_names, (int(x) for x in out)))
+
+    set_device.__doc__, stats.__doc__ = set_doc, stats_doc
+    for fn, name in ((set_device, "set_%s_device"), (device_enabled, "%s_device_enabled"), (stats, "%s_stats")):
+        fn.__name__ = fn.__qualname__ = name % stem
+    return set_device, device_enabled, stats
+
+
 EXTRA_JOB_DTYPE = np.dtype([("q_off", np.uint32), ("t_off", np.uint32), ("cig_off", np.uint32), ("n_cigar", np.int32)])                       # wm_extra_job_t
 EXTRA_POS_DTYPE = np.dtype([("qwin_off", np.int64), ("qwin_len", np.int32), ("q_pos", np.int32), ("rid", np.int32), ("t_pos", np.int32),
                             ("cig_off", np.uint32), ("n_cigar", np.int32)])                                                                      # wm_extra_pos_t
@@ -391,78 +418,30 @@ def extra_tile_cols():
     return int(lib().wm_extra_tile_cols())
 
 
-def set_extra_device(on):
+set_extra_device, extra_device_enabled, extra_stats = _device_switch("extra", EXTRA_STAT_NAMES,
     """wm_set_extra_device: the mapper defers its regions' final scans (mm_update_extra's walk) to one batched device call per read (off by default;
-    on < 0: back to what WM_EXTRA_DEV in the environment says). Read when a mapping call starts; results never depend on it."""
-    lib().wm_set_extra_device.argtypes = [C.c_int]
-    lib().wm_set_extra_device.restype = None
-    lib().wm_set_extra_device(int(on))
-
-
-def extra_device_enabled():
-    lib().wm_extra_device_enabled.restype = C.c_int
-    return bool(lib().wm_extra_device_enabled())
-
-
-def extra_stats(reset=False):
-    """wm_extra_stats: regions deferred / walked on the device / walked on the host while the switch was on, batched device calls, columns, microseconds"""
-    out = np.zeros(6, np.uint64)
-    lib().wm_extra_stats.argtypes = [C.c_void_p, C.c_int]
-    lib().wm_extra_stats.restype = None
-    lib().wm_extra_stats(out.ctypes.data, 1 if reset else 0)
-    return dict(zip(EXTRA_STAT_NAMES, (int(x) for x in out)))
+    on < 0: back to what WM_EXTRA_DEV in the environment says). Read when a mapping call starts; results never depend on it.""",
+    """wm_extra_stats: regions deferred / walked on the device / walked on the host while the switch was on, batched device calls, columns, microseconds""")
 
 
 FIX_STAT_NAMES = ("deferred", "on_device", "on_host", "early_on_host", "calls", "device_us", "columns")
 
 
-def set_fix_device(on):
+set_fix_device, fix_device_enabled, fix_stats = _device_switch("fix", FIX_STAT_NAMES,
     """wm_set_fix_device: the mapper defers BOTH halves of mm_update_extra — mm_fix_cigar and the scan — to one batched wm_fix_extra_batch_pos per read (off by
-    default; on < 0: back to what WM_FIX_DEV in the environment says). Read when a mapping call starts; results never depend on it."""
-    lib().wm_set_fix_device.argtypes = [C.c_int]
-    lib().wm_set_fix_device.restype = None
-    lib().wm_set_fix_device(int(on))
-
-
-def fix_device_enabled():
-    lib().wm_fix_device_enabled.restype = C.c_int
-    return bool(lib().wm_fix_device_enabled())
-
-
-def fix_stats(reset=False):
+    default; on < 0: back to what WM_FIX_DEV in the environment says). Read when a mapping call starts; results never depend on it.""",
     """wm_fix_stats: regions whose fix was deferred / fixed on the device / fixed on the host by the batched request / fixed on the host early because an inversion
-    test read them, batched device calls, microseconds, alignment columns walked by those calls"""
-    out = np.zeros(7, np.uint64)
-    lib().wm_fix_stats.argtypes = [C.c_void_p, C.c_int]
-    lib().wm_fix_stats.restype = None
-    lib().wm_fix_stats(out.ctypes.data, 1 if reset else 0)
-    return dict(zip(FIX_STAT_NAMES, (int(x) for x in out)))
+    test read them, batched device calls, microseconds, alignment columns walked by those calls""")
 
 
 EQX_RES_DTYPE = np.dtype([("off", np.uint64), ("n_cigar", np.int32), ("in_place", np.int32)])                                                 # wm_eqx_res_t
 EQX_STAT_NAMES = ("deferred", "on_device", "on_host", "calls", "columns", "device_us")
 
 
-def set_eqx_device(on):
+set_eqx_device, eqx_device_enabled, eqx_stats = _device_switch("eqx", EQX_STAT_NAMES,
     """wm_set_eqx_device: under MM_F_EQX the mapper defers the = / X rewriting of final CIGARs (mm_update_cigar_eqx) to one batched wm_eqx_batch_pos per read (off
-    by default; on < 0: back to what WM_EQX_DEV in the environment says). Read when a mapping call starts; results never depend on it."""
-    lib().wm_set_eqx_device.argtypes = [C.c_int]
-    lib().wm_set_eqx_device.restype = None
-    lib().wm_set_eqx_device(int(on))
-
-
-def eqx_device_enabled():
-    lib().wm_eqx_device_enabled.restype = C.c_int
-    return bool(lib().wm_eqx_device_enabled())
-
-
-def eqx_stats(reset=False):
-    """wm_eqx_stats: regions deferred / rewritten on the device / rewritten on the host by the batched request, batched device calls, M columns, microseconds"""
-    out = np.zeros(6, np.uint64)
-    lib().wm_eqx_stats.argtypes = [C.c_void_p, C.c_int]
-    lib().wm_eqx_stats.restype = None
-    lib().wm_eqx_stats(out.ctypes.data, 1 if reset else 0)
-    return dict(zip(EQX_STAT_NAMES, (int(x) for x in out)))
+    by default; on < 0: back to what WM_EQX_DEV in the environment says). Read when a mapping call starts; results never depend on it.""",
+    """wm_eqx_stats: regions deferred / rewritten on the device / rewritten on the host by the batched request, batched device calls, M columns, microseconds""")
 
 
 CS_RES_DTYPE = np.dtype([("off", np.uint64), ("len", np.uint32), ("pad", np.int32)])                                                       # wm_cs_res_t
@@ -470,26 +449,10 @@ CS_SHORT, CS_LONG, CS_MD = 0, 1, 2                                              
 CS_STAT_NAMES = ("deferred", "on_device", "on_host", "calls", "bytes", "device_us")
 
 
-def set_cs_device(on):
+set_cs_device, cs_device_enabled, cs_stats = _device_switch("cs", CS_STAT_NAMES,
     """wm_set_cs_device: under MM_F_OUT_CS / MM_F_OUT_MD the mapper has the bodies of a read's cs:Z / MD:Z tags produced by one batched wm_cs_batch_pos per read (off
-    by default; on < 0: back to what WM_CS_DEV in the environment says). Read when a mapping call starts; results never depend on it."""
-    lib().wm_set_cs_device.argtypes = [C.c_int]
-    lib().wm_set_cs_device.restype = None
-    lib().wm_set_cs_device(int(on))
-
-
-def cs_device_enabled():
-    lib().wm_cs_device_enabled.restype = C.c_int
-    return bool(lib().wm_cs_device_enabled())
-
-
-def cs_stats(reset=False):
-    """wm_cs_stats: regions deferred / served on the device / served on the host by the batched request, batched device calls, bytes produced, microseconds"""
-    out = np.zeros(6, np.uint64)
-    lib().wm_cs_stats.argtypes = [C.c_void_p, C.c_int]
-    lib().wm_cs_stats.restype = None
-    lib().wm_cs_stats(out.ctypes.data, 1 if reset else 0)
-    return dict(zip(CS_STAT_NAMES, (int(x) for x in out)))
+    by default; on < 0: back to what WM_CS_DEV in the environment says). Read when a mapping call starts; results never depend on it.""",
+    """wm_cs_stats: regions deferred / served on the device / served on the host by the batched request, batched device calls, bytes produced, microseconds""")
 
 
 def set_ksw_routing(on=-1, rows4=-1, rows8=-1):
