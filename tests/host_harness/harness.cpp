@@ -14,9 +14,11 @@
 #include "../../winnowmap_amd/csrc/host/wm_pipeline.cpp"
 #include "../../oracle/wm_oracle.h"
 #include "../../winnowmap_amd/csrc/reads2bit.h"
+#include "../../winnowmap_amd/csrc/host/wm_final_plan.h"
 #include <fstream>
 #include <set>
 #include <stdexcept>
+#include <stdarg.h>
 
 using namespace wm;
 
@@ -679,6 +681,177 @@ extern "C" int wmh_hub_selftest(int n_threads, int n_fibers, int splice)
 		size_t served = 0;
 		for (int i = 0; i < n_fibers; ++i) served += first[i].u.size() + second[i].u.size();
 		HUB_CHECK(served >= 1 && served < 2 * (size_t)n_fibers);      // (the batch that threw served nobody; every other batch served its requests)
+	}
+	return 0;
+}
+
+// ---- the batch planner of the final-CIGAR device calls on its own (host/wm_final_plan.h): every expectation below is a literal table ----
+namespace {
+int fp_code = 0, fp_calls = 0;
+char fp_msg[512] = "";
+int fp_err(int code, const char *fmt, ...)         // set_err's signature: records instead
+{
+	va_list ap;
+	va_start(ap, fmt);
+	vsnprintf(fp_msg, sizeof(fp_msg), fmt, ap);
+	va_end(ap);
+	fp_code = code; ++fp_calls;
+	return code;
+}
+int fp_measured = 0;                               // calls of the measure below
+int fp_measure(int, const uint32_t *cig, int nc, int64_t *qlen, int64_t *tlen, int64_t *cols)      // M / I / D lengths, nothing refused
+{
+	++fp_measured;
+	for (int k = 0; k < nc; ++k) {
+		const uint32_t op = cig[k] & 0xf, len = cig[k] >> 4;
+		if (op == 0) { *qlen += len; *tlen += len; *cols += len; }
+		else if (op == 1) { *qlen += len; *cols += len; }
+		else if (op == 2) { *tlen += len; *cols += len; }
+	}
+	return 0;
+}
+bool fp_pairs(const std::vector<wm_final_pair> &v, std::initializer_list<std::pair<int, int>> want)
+{
+	if (v.size() != want.size()) return false;
+	size_t i = 0;
+	for (const auto &w : want) { if (v[i].x != w.first || v[i].y != w.second) return false; ++i; }
+	return true;
+}
+bool fp_zero(const wm_extra_djob_t &d) { static const wm_extra_djob_t z = {}; return memcmp(&d, &z, sizeof(d)) == 0; }
+constexpr uint32_t fp_M(uint32_t len) { return len << 4; }
+constexpr uint32_t fp_I(uint32_t len) { return len << 4 | 1; }
+constexpr uint32_t fp_D(uint32_t len) { return len << 4 | 2; }
+}
+
+#define FP_CHECK(c) do { if (!(c)) { fprintf(stderr, "[harness] final plan selftest: %s fails (line %d; last message \"%s\")\n", #c, __LINE__, fp_msg); return -__LINE__; } } while (0)
+extern "C" int wmh_final_plan_selftest(void)
+{
+	const int LMIN = 128, TILE = 64;
+	const uint32_t seq_len[2] = { 500, 300 };
+	const uint64_t seq_off[2] = { 0, 512 };
+	const FinalView view = { 1000, seq_len, seq_off, 2 };
+	FinalPlan plan;
+	fp_calls = 0; fp_msg[0] = 0;
+	{   // routing: columns 0 (empty CIGAR), 127, 128, 129, 64
+		const uint32_t cig[5] = { fp_M(127), fp_M(100), fp_I(28), fp_M(129), fp_M(64) };
+		const wm_extra_job_t jobs[5] = { { 0, 0, 0, 0 }, { 0, 0, 0, 1 }, { 0, 0, 1, 2 }, { 0, 0, 3, 1 }, { 0, 0, 4, 1 } };
+		static const uint32_t pre_off[2][5] = { { 0, 1, 3, 6, 8 }, { 0, 2, 5, 9, 12 } };
+		static const size_t n_pre[2] = { 10, 15 };
+		static const int32_t tile0[5] = { 0, 0, 0, 2, 0 };
+		for (int slack = 1; slack <= 2; ++slack) {
+			FP_CHECK(final_plan(view, 5, jobs, 1000, 0, cig, 5, slack, LMIN, TILE, fp_err, fp_measure, plan) == WM_OK);
+			FP_CHECK(plan.dj.size() == 5 && plan.order == (std::vector<int>{ 0, 1, 4 }));
+			FP_CHECK(fp_pairs(plan.tmap, { { 2, 0 }, { 2, 1 }, { 3, 0 }, { 3, 1 }, { 3, 2 } }));
+			FP_CHECK(fp_pairs(plan.lmap, { { 2, 2 }, { 3, 3 } }));
+			for (int i = 0; i < 5; ++i) {
+				const wm_extra_djob_t &d = plan.dj[i];
+				FP_CHECK(d.tile0 == tile0[i] && d.pre_off == pre_off[slack - 1][i] && d.cig_off == jobs[i].cig_off && d.n_cigar == jobs[i].n_cigar);
+				FP_CHECK(d.q_base == 0 && d.t_base == 0 && d.q_pos == 0 && d.q_len == 0);
+			}
+			FP_CHECK(plan.n_pre == n_pre[slack - 1]);
+		}
+		// long_min = 0: the empty job stays short, every other one is long
+		static const int32_t tile0_all[5] = { 0, 0, 2, 4, 7 };
+		FP_CHECK(final_plan(view, 5, jobs, 1000, 0, cig, 5, 1, 0, TILE, fp_err, fp_measure, plan) == WM_OK);
+		FP_CHECK(plan.order == (std::vector<int>{ 0 }));
+		FP_CHECK(fp_pairs(plan.tmap, { { 1, 0 }, { 1, 1 }, { 2, 0 }, { 2, 1 }, { 3, 0 }, { 3, 1 }, { 3, 2 }, { 4, 0 } }));
+		FP_CHECK(fp_pairs(plan.lmap, { { 1, 2 }, { 2, 2 }, { 3, 3 }, { 4, 1 } }));
+		for (int i = 0; i < 5; ++i) FP_CHECK(plan.dj[i].tile0 == tile0_all[i]);
+		// two jobs on one CIGAR range: a prefix slot each
+		const wm_extra_job_t twice[2] = { { 0, 0, 1, 2 }, { 0, 0, 1, 2 } };
+		FP_CHECK(final_plan(view, 2, twice, 1000, 0, cig, 5, 1, LMIN, TILE, fp_err, fp_measure, plan) == WM_OK);
+		FP_CHECK(plan.dj[0].pre_off == 0 && plan.dj[1].pre_off == 3 && plan.n_pre == 6 && plan.dj[0].cig_off == 1 && plan.dj[1].cig_off == 1);
+		FP_CHECK(plan.dj[0].tile0 == 0 && plan.dj[1].tile0 == 2 && fp_pairs(plan.lmap, { { 0, 2 }, { 1, 2 } }));
+		FP_CHECK(fp_calls == 0);
+	}
+	// operands: one CIGAR of 15 query and 13 target bases
+	const uint32_t cig[3] = { fp_M(10), fp_I(5), fp_D(3) };
+	const wm_extra_pos_t good = { 100, 50, 0, 0, 0, 0, 3 };
+	{   // the accepted edges, position form
+		const wm_extra_pos_t pos[5] = {
+			{ 100, 50, -16, 0, 0, 0, 3 },            // q_pos == -16
+			{ 100, 50, 101, 1, 7, 0, 3 },            // q_pos + qlen == 2 * qwin_len + 16
+			{ 100, 50, 0, 1, 287, 0, 3 },            // t_pos + tlen == seq_len[rid]
+			{ 950, 50, 0, 0, 0, 0, 3 },              // qwin_off + qwin_len == reads_bytes
+			{ -5, -1, -1000, 99, -3, 3, 0 } };       // no CIGAR: the positions are not looked at
+		static const long long q_base[5] = { 100, 100, 100, 950, 0 }, t_base[5] = { 0, 519, 799, 0, 0 };
+		static const int32_t q_pos[5] = { -16, 101, 0, 0, 0 }, q_len[5] = { 50, 50, 50, 50, 0 };
+		static const uint32_t pre_off[5] = { 0, 4, 8, 12, 16 };
+		FP_CHECK(final_plan(view, 5, 0, 0, pos, cig, 3, 1, LMIN, TILE, fp_err, fp_measure, plan) == WM_OK);
+		FP_CHECK(fp_calls == 0 && plan.order == (std::vector<int>{ 0, 1, 2, 3, 4 }) && plan.tmap.empty() && plan.lmap.empty() && plan.n_pre == 17);
+		for (int i = 0; i < 5; ++i) {
+			const wm_extra_djob_t &d = plan.dj[i];
+			FP_CHECK(d.q_base == q_base[i] && d.t_base == t_base[i] && d.q_pos == q_pos[i] && d.q_len == q_len[i] && d.pre_off == pre_off[i] && d.tile0 == 0);
+			FP_CHECK(d.cig_off == pos[i].cig_off && d.n_cigar == pos[i].n_cigar);
+		}
+		// ... and byte form: both operands end with seqs
+		const wm_extra_job_t jobs[2] = { { 85, 0, 0, 3 }, { 0, 87, 0, 3 } };
+		FP_CHECK(final_plan(view, 2, jobs, 100, 0, cig, 3, 1, LMIN, TILE, fp_err, fp_measure, plan) == WM_OK);
+		FP_CHECK(fp_calls == 0 && plan.dj[0].q_base == 85 && plan.dj[0].t_base == 0 && plan.dj[1].q_base == 0 && plan.dj[1].t_base == 87);
+	}
+	{   // one step past each edge: job 1 of three is refused with WM_EINVAL and named, job 0 is planned, job 2 is not
+		const FinalView wide = { (size_t)1 << 31, seq_len, seq_off, 2 };
+		struct { wm_extra_pos_t bad; const FinalView *v; const char *what; } const cases[] = {
+			{ { 100, 50, -17, 0, 0, 0, 3 }, &view, "query bases" },                 // q_pos == -17
+			{ { 100, 50, 102, 0, 0, 0, 3 }, &view, "query bases" },                 // q_pos + qlen == 2 * qwin_len + 17
+			{ { 100, 50, 0, 1, 288, 0, 3 }, &view, "target bases" },                // t_pos + tlen == seq_len[rid] + 1
+			{ { 951, 50, 0, 0, 0, 0, 3 }, &view, "resident reads" },                // qwin_off + qwin_len == reads_bytes + 1
+			{ { 100, 50, 0, 2, 0, 0, 3 }, &view, "target bases" },                  // rid == n_seq
+			{ { 100, 50, 0, -1, 0, 0, 3 }, &view, "target bases" },                 // rid < 0
+			{ { 100, 50, 0, 0, -1, 0, 3 }, &view, "target bases" },                 // t_pos < 0
+			{ { 0, 1 << 30, 0, 0, 0, 0, 3 }, &wide, "resident reads" },             // qwin_len == 2^30, inside the reads
+			{ { 100, 50, 0, 0, 0, 0, -1 }, &view, "CIGAR ops" },                    // nc < 0
+			{ { 100, 50, 0, 0, 0, 1, 3 }, &view, "CIGAR ops" } };                   // cig_off + nc == n_ops + 1
+		for (const auto &cs : cases) {
+			const wm_extra_pos_t pos[3] = { good, cs.bad, good };
+			fp_calls = 0; fp_code = 0;
+			FP_CHECK(final_plan(*cs.v, 3, 0, 0, pos, cig, 3, 1, LMIN, TILE, fp_err, fp_measure, plan) == WM_EINVAL);
+			FP_CHECK(fp_calls == 1 && fp_code == WM_EINVAL && strncmp(fp_msg, "job 1:", 6) == 0 && strstr(fp_msg, cs.what));
+			FP_CHECK(plan.order == (std::vector<int>{ 0 }) && plan.tmap.empty() && plan.lmap.empty() && plan.dj.size() == 3 && fp_zero(plan.dj[2]));
+			FP_CHECK(plan.dj[0].q_base == 100 && plan.dj[0].n_cigar == 3);
+		}
+		{   // (the wide view accepts what only its qwin_len rule refused: one less)
+			const wm_extra_pos_t pos[1] = { { 0, (1 << 30) - 1, 0, 0, 0, 0, 3 } };
+			fp_calls = 0;
+			FP_CHECK(final_plan(wide, 1, 0, 0, pos, cig, 3, 1, LMIN, TILE, fp_err, fp_measure, plan) == WM_OK && fp_calls == 0);
+		}
+		static const wm_extra_job_t bad_bytes[2] = { { 86, 0, 0, 3 }, { 0, 88, 0, 3 } };          // q_off + qlen, t_off + tlen == seqs_bytes + 1
+		for (const wm_extra_job_t &bad : bad_bytes) {
+			const wm_extra_job_t jobs[3] = { { 0, 0, 0, 3 }, bad, { 0, 0, 0, 3 } };
+			fp_calls = 0; fp_code = 0;
+			FP_CHECK(final_plan(view, 3, jobs, 100, 0, cig, 3, 1, LMIN, TILE, fp_err, fp_measure, plan) == WM_EINVAL);
+			FP_CHECK(fp_calls == 1 && fp_code == WM_EINVAL && strncmp(fp_msg, "job 1:", 6) == 0 && strstr(fp_msg, "more than seqs holds"));
+			FP_CHECK(plan.order == (std::vector<int>{ 0 }) && plan.tmap.empty() && plan.lmap.empty() && fp_zero(plan.dj[2]));
+		}
+	}
+	{   // a measure that refuses job 1 wins over job 1's bad operand and loses to its bad CIGAR range
+		int measured = 0;
+		auto refuses = [&](int i, const uint32_t *cg, int nc, int64_t *qlen, int64_t *tlen, int64_t *cols) {
+			++measured;
+			if (i == 1) return fp_err(WM_EINVAL, "job %d: the measure refuses", i);
+			return fp_measure(i, cg, nc, qlen, tlen, cols);
+		};
+		const wm_extra_pos_t bad_operand[3] = { good, { 100, 50, -17, 0, 0, 0, 3 }, good }, bad_range[3] = { good, { 100, 50, 0, 0, 0, 1, 3 }, good };
+		fp_calls = 0;
+		FP_CHECK(final_plan(view, 3, 0, 0, bad_operand, cig, 3, 1, LMIN, TILE, fp_err, refuses, plan) == WM_EINVAL);
+		FP_CHECK(fp_calls == 1 && measured == 2 && strcmp(fp_msg, "job 1: the measure refuses") == 0);
+		FP_CHECK(plan.order == (std::vector<int>{ 0 }) && fp_zero(plan.dj[1]) && fp_zero(plan.dj[2]) && plan.n_pre == 4);
+		fp_calls = 0; measured = 0;
+		FP_CHECK(final_plan(view, 3, 0, 0, bad_range, cig, 3, 1, LMIN, TILE, fp_err, refuses, plan) == WM_EINVAL);
+		FP_CHECK(fp_calls == 1 && measured == 1 && strncmp(fp_msg, "job 1: CIGAR ops", 16) == 0);
+	}
+	{   // the tile cap: refused before the job's tiles go in (the columns are claimed by the measure; no CIGAR is that long)
+		static const int64_t claimed[2] = { 128, 64 * (((int64_t)1 << 28) - 2) };
+		auto claims = [&](int i, const uint32_t*, int, int64_t*, int64_t*, int64_t *cols) { *cols = claimed[i]; return 0; };
+		const wm_extra_job_t jobs[2] = { { 0, 0, 0, 1 }, { 0, 0, 0, 1 } };
+		fp_calls = 0; fp_code = 0;
+		FP_CHECK(final_plan(view, 2, jobs, 1000, 0, cig, 3, 1, LMIN, TILE, fp_err, claims, plan) == WM_ENOMEM);
+		FP_CHECK(fp_calls == 1 && fp_code == WM_ENOMEM && strstr(fp_msg, "2^28 tiles"));
+		FP_CHECK(fp_pairs(plan.tmap, { { 0, 0 }, { 0, 1 } }) && fp_pairs(plan.lmap, { { 0, 2 } }) && plan.tmap.capacity() < 1024 && plan.order.empty());
+		auto claims_all = [&](int, const uint32_t*, int, int64_t*, int64_t*, int64_t *cols) { *cols = 64 * ((int64_t)1 << 28); return 0; };
+		fp_calls = 0;
+		FP_CHECK(final_plan(view, 1, jobs, 1000, 0, cig, 3, 1, LMIN, TILE, fp_err, claims_all, plan) == WM_ENOMEM);
+		FP_CHECK(fp_calls == 1 && plan.tmap.empty() && plan.lmap.empty() && plan.tmap.capacity() < 1024);
 	}
 	return 0;
 }

@@ -26,38 +26,10 @@
 #include <stdint.h>
 #include "../../include/wm_gpu.h"
 #include "reads2bit.h"
+#include "host/wm_final_plan.h"
 
 #define WM_EXTRA_NEG (-0x40000000)          // m of the identity
-#define WM_EXTRA_GAP 64                     // bases of an I / D op per column
-
-// one job as the kernels see it. Byte form: q_base / t_base = offsets of the operands in the call's sequence slab. Position form: q_base = first base of the (sub)read
-// in the resident read codes, q_len its length, q_pos the two-strand index of the alignment's first query base; t_base = index of its first target base in the 4-bit S array
-typedef struct { long long q_base, t_base; uint32_t cig_off, pre_off; int32_t n_cigar, q_pos, q_len, tile0; } wm_extra_djob_t;
-
-// what the host needs to know of a job before it goes out (64-bit): columns, bases consumed, and the bound of the limit above
-// (for mm_fix_cigar in front of the scan, fix_kernel.h: total = all lengths added up; bad_zero = the first op of length 0 and code >= 3, or -1)
-typedef struct { int64_t cols, qlen, tlen, abs_sum, total; int32_t bad_zero; } wm_extra_measure_t;
-static inline wm_extra_measure_t wm_extra_measure(const uint32_t *cig, int n, const wm_extra_score_t *sc)
-{
-	wm_extra_measure_t r = { 0, 0, 0, 0, 0, -1 };
-	int64_t mx = sc->match < 0 ? -(int64_t)sc->match : sc->match, m_cols = 0;
-	if (mx < (sc->mismatch < 0 ? -(int64_t)sc->mismatch : sc->mismatch)) mx = sc->mismatch < 0 ? -(int64_t)sc->mismatch : sc->mismatch;
-	if (mx < (sc->ambi < 0 ? -(int64_t)sc->ambi : sc->ambi)) mx = sc->ambi < 0 ? -(int64_t)sc->ambi : sc->ambi;
-	for (int k = 0; k < n; ++k) {
-		const int64_t op = cig[k] & 0xf, len = cig[k] >> 4;
-		r.total += len;
-		if (len == 0 && op >= 3 && r.bad_zero < 0) r.bad_zero = k;
-		if (op == 0) { m_cols += len; r.qlen += len; r.tlen += len; }
-		else if (op == 1 || op == 2) {
-			const int64_t g = (int64_t)sc->q + (int64_t)sc->e * len;
-			r.cols += len > WM_EXTRA_GAP ? (len + WM_EXTRA_GAP - 1) / WM_EXTRA_GAP : 1;
-			r.abs_sum += g < 0 ? -g : g;
-			if (op == 1) r.qlen += len; else r.tlen += len;
-		} else if (op == 3) r.tlen += len;
-	}
-	r.cols += m_cols; r.abs_sum += mx * m_cols;
-	return r;
-}
+// (WM_EXTRA_GAP — bases of an I / D op per column —, the job record wm_extra_djob_t and the host-side wm_extra_measure live with the batch planner: host/wm_final_plan.h)
 
 namespace wmk {
 using namespace simt;

@@ -1,17 +1,16 @@
 // wm_cs.hip — libwmgpu.so, cs / MD unit: the bodies of the cs:Z / MD:Z tags (write_cs_core, write_MD_core, src/format.c:141-218, under --cs, --cs=long, --MD) over
 // batches of regions' final CIGARs — wm_cs_batch, wm_cs_batch_pos of include/wm_gpu.h. The column space, the fold and the two passes are in cs_kernel.h, the
-// specification in cigar_cs.h; here are the kernel entry points, validation (the rules of wm_eqx.hip, and what the reference asserts), the split into the two
-// classes by the values of wm_extra_set_routing, and the launches. (The mapper's switch and its counters live with the host mapper: host/wm_ops.cpp.)
+// specification in cigar_cs.h; here are the kernel entry points, what this pass measures and refuses of a job (what the reference asserts among it), and the launches;
+// validation of ranges and operands and the split into the two classes by the values of wm_extra_set_routing are the planner's (host/wm_final_plan.h), the common uploads
+// final_stage's (wm_rt.hip). (The mapper's switch and its counters live with the host mapper: host/wm_ops.cpp.)
 #include "wm_rt.h"
 #include "simt.h"
 #include "cs_kernel.h"
-
-int extra_long_min_cols();          // wm_extra.hip
+#include "final_src.h"
 
 // ======================================================================================================
 // kernels (one wavefront per workgroup)
 // ======================================================================================================
-struct cs_dev_src { const uint8_t *seqs; const uint64_t *pk, *nm; const uint32_t *S; };
 struct cs_dev_pre { const uint32_t *cig; int *cS, *qS, *tS, *wS; };
 
 #define CS_JOB(j) \
@@ -26,32 +25,20 @@ __global__ __launch_bounds__(64) void cs_prefix_kernel(const wm_extra_djob_t *__
 }
 // count, short class: workgroup g walks all tiles of job order[g] -> cnt[j]
 template <bool POS>
-__global__ __launch_bounds__(64) void cs_short_count_kernel(const wm_extra_djob_t *__restrict__ jobs, const int *__restrict__ order, cs_dev_src D, cs_dev_pre P, int mode, int tile_cols, int *cnt)
+__global__ __launch_bounds__(64) void cs_short_count_kernel(const wm_extra_djob_t *__restrict__ jobs, const int *__restrict__ order, final_dev_src D, cs_dev_pre P, int mode, int tile_cols, int *cnt)
 {
 	const int j = order[blockIdx.x];
 	CS_JOB(j);
-	if constexpr (POS) {
-		const wmk::extra_src_pos S = { D.pk, D.nm, D.S, jb.q_base, jb.t_base, jb.q_pos, jb.q_len };
-		wmk::cs_short_count(S, mode, cS, qS, tS, wS, jb.n_cigar, tile_cols, cnt + j);
-	} else {
-		const wmk::extra_src_bytes S = { D.seqs, jb.q_base, jb.t_base };
-		wmk::cs_short_count(S, mode, cS, qS, tS, wS, jb.n_cigar, tile_cols, cnt + j);
-	}
+	with_src<POS>(D, jb, [&](const auto &S) { wmk::cs_short_count(S, mode, cS, qS, tS, wS, jb.n_cigar, tile_cols, cnt + j); });
 }
 // count, long class: workgroup g folds tile tmap[g].y of job tmap[g].x into part[4 g ..]; then one workgroup per long job turns its tiles' summaries into carries
 template <bool POS>
-__global__ __launch_bounds__(64) void cs_tile_count_kernel(const wm_extra_djob_t *__restrict__ jobs, const int2 *__restrict__ tmap, cs_dev_src D, cs_dev_pre P, int mode, int tile_cols, int *part)
+__global__ __launch_bounds__(64) void cs_tile_count_kernel(const wm_extra_djob_t *__restrict__ jobs, const int2 *__restrict__ tmap, final_dev_src D, cs_dev_pre P, int mode, int tile_cols, int *part)
 {
 	const int2 tm = tmap[blockIdx.x];
 	CS_JOB(tm.x);
 	int *out = part + (size_t)blockIdx.x * 4;
-	if constexpr (POS) {
-		const wmk::extra_src_pos S = { D.pk, D.nm, D.S, jb.q_base, jb.t_base, jb.q_pos, jb.q_len };
-		wmk::cs_long_count(S, mode, cS, qS, tS, wS, jb.n_cigar, tile_cols, tm.y, out);
-	} else {
-		const wmk::extra_src_bytes S = { D.seqs, jb.q_base, jb.t_base };
-		wmk::cs_long_count(S, mode, cS, qS, tS, wS, jb.n_cigar, tile_cols, tm.y, out);
-	}
+	with_src<POS>(D, jb, [&](const auto &S) { wmk::cs_long_count(S, mode, cS, qS, tS, wS, jb.n_cigar, tile_cols, tm.y, out); });
 }
 __global__ __launch_bounds__(64) void cs_combine_kernel(const wm_extra_djob_t *__restrict__ jobs, const int2 *__restrict__ lmap, int *part, int *cnt)
 {
@@ -66,35 +53,23 @@ __global__ __launch_bounds__(64) void cs_job_scan_kernel(const int *__restrict__
 }
 // write
 template <bool POS>
-__global__ __launch_bounds__(64) void cs_short_write_kernel(const wm_extra_djob_t *__restrict__ jobs, const int *__restrict__ order, cs_dev_src D, cs_dev_pre P, int mode, int tile_cols,
+__global__ __launch_bounds__(64) void cs_short_write_kernel(const wm_extra_djob_t *__restrict__ jobs, const int *__restrict__ order, final_dev_src D, cs_dev_pre P, int mode, int tile_cols,
                                                              const wm_cs_res_t *__restrict__ res, uint8_t *out)
 {
 	const int j = order[blockIdx.x];
 	CS_JOB(j);
 	uint8_t *o = out + res[j].off;
-	if constexpr (POS) {
-		const wmk::extra_src_pos S = { D.pk, D.nm, D.S, jb.q_base, jb.t_base, jb.q_pos, jb.q_len };
-		wmk::cs_short_write(S, mode, cS, qS, tS, wS, jb.n_cigar, tile_cols, o);
-	} else {
-		const wmk::extra_src_bytes S = { D.seqs, jb.q_base, jb.t_base };
-		wmk::cs_short_write(S, mode, cS, qS, tS, wS, jb.n_cigar, tile_cols, o);
-	}
+	with_src<POS>(D, jb, [&](const auto &S) { wmk::cs_short_write(S, mode, cS, qS, tS, wS, jb.n_cigar, tile_cols, o); });
 }
 template <bool POS>
-__global__ __launch_bounds__(64) void cs_tile_write_kernel(const wm_extra_djob_t *__restrict__ jobs, const int2 *__restrict__ tmap, cs_dev_src D, cs_dev_pre P, int mode, int tile_cols,
+__global__ __launch_bounds__(64) void cs_tile_write_kernel(const wm_extra_djob_t *__restrict__ jobs, const int2 *__restrict__ tmap, final_dev_src D, cs_dev_pre P, int mode, int tile_cols,
                                                             const int *__restrict__ part, const wm_cs_res_t *__restrict__ res, uint8_t *out)
 {
 	const int2 tm = tmap[blockIdx.x];
 	CS_JOB(tm.x);
 	uint8_t *o = out + res[tm.x].off;
 	const int *pt = part + (size_t)blockIdx.x * 4;
-	if constexpr (POS) {
-		const wmk::extra_src_pos S = { D.pk, D.nm, D.S, jb.q_base, jb.t_base, jb.q_pos, jb.q_len };
-		wmk::cs_long_write(S, mode, cS, qS, tS, wS, jb.n_cigar, tile_cols, tm.y, pt, o);
-	} else {
-		const wmk::extra_src_bytes S = { D.seqs, jb.q_base, jb.t_base };
-		wmk::cs_long_write(S, mode, cS, qS, tS, wS, jb.n_cigar, tile_cols, tm.y, pt, o);
-	}
+	with_src<POS>(D, jb, [&](const auto &S) { wmk::cs_long_write(S, mode, cS, qS, tS, wS, jb.n_cigar, tile_cols, tm.y, pt, o); });
 }
 
 // ======================================================================================================
@@ -116,15 +91,8 @@ try {
 	HIPCHK(hipSetDevice(c->device));
 	ArenaMark mark(c);
 	const size_t nj = (size_t)n_jobs;
-	std::vector<wm_extra_djob_t> dj(nj);
-	std::vector<int> order; std::vector<int2> tmap, lmap;
-	size_t n_pre = 0;
 	uint64_t bound_all = 0;
-	for (int i = 0; i < n_jobs; ++i) {
-		const uint32_t cig_off = pos ? pos[i].cig_off : jobs[i].cig_off;
-		const int32_t nc = pos ? pos[i].n_cigar : jobs[i].n_cigar;
-		if (nc < 0 || (uint64_t)cig_off + (uint64_t)nc > n_ops) return set_err(WM_EINVAL, "job %d: CIGAR ops [%u, %u + %d) outside the %zu ops of the call", i, cig_off, cig_off, nc, n_ops);
-		const uint32_t *cg = cigars + cig_off;
+	auto measure = [&](int i, const uint32_t *cg, int nc, int64_t *qlen_out, int64_t *tlen_out, int64_t *cols_out) {
 		const int bad = wm_cigar_cs_check(mode, cg, nc);
 		if (bad >= 0) {
 			if ((cg[bad] & 0xf) == 3) return set_err(WM_EINVAL, "job %d: op %d is an N of length %u, shorter than the 2 bases a cs tag prints on either side (src/format.c:180)", i, bad, cg[bad] >> 4);
@@ -143,71 +111,35 @@ try {
 		if (bound >= ((int64_t)1 << 31) || cols >= ((int64_t)1 << 31) - 64 * (int64_t)tile_cols || qlen >= ((int64_t)1 << 31) || tlen >= ((int64_t)1 << 31))
 			return set_err(WM_EINVAL, "job %d: the tag of this CIGAR can reach %lld bytes, 2^31 or more", i, (long long)bound);
 		bound_all += (uint64_t)bound;
-		wm_extra_djob_t &d = dj[i];
-		memset(&d, 0, sizeof(d));
-		d.cig_off = cig_off; d.n_cigar = nc; d.pre_off = (uint32_t)n_pre;
-		n_pre += (size_t)nc + 2;
-		if (n_pre >= ((size_t)1 << 31)) return set_err(WM_ENOMEM, "batch holds 2^31 CIGAR ops or more; split it");
-		if (pos) {
-			const wm_extra_pos_t &s = pos[i];
-			if (nc > 0) {
-				if (s.qwin_off < 0 || s.qwin_len < 0 || s.qwin_len >= (1 << 30) || (uint64_t)s.qwin_off + (uint64_t)s.qwin_len > c->reads_bytes)
-					return set_err(WM_EINVAL, "job %d: the (sub)read lies outside the resident reads", i);
-				if ((int64_t)s.q_pos < -16 || (int64_t)s.q_pos + qlen > 2 * (int64_t)s.qwin_len + 16)
-					return set_err(WM_EINVAL, "job %d: the CIGAR consumes %lld query bases from two-strand position %d of a read of %d bases", i, (long long)qlen, s.q_pos, s.qwin_len);
-				if (s.rid < 0 || (size_t)s.rid >= c->seq_len.size() || s.t_pos < 0 || (int64_t)s.t_pos + tlen > (int64_t)c->seq_len[s.rid])
-					return set_err(WM_EINVAL, "job %d: the CIGAR consumes %lld target bases from base %d of contig %d", i, (long long)tlen, s.t_pos, s.rid);
-				d.q_base = s.qwin_off; d.q_pos = s.q_pos; d.q_len = s.qwin_len; d.t_base = (long long)c->seq_off[s.rid] + s.t_pos;
-			}
-		} else {
-			const wm_extra_job_t &s = jobs[i];
-			if (nc > 0 && ((uint64_t)s.q_off + (uint64_t)qlen > seqs_bytes || (uint64_t)s.t_off + (uint64_t)tlen > seqs_bytes))
-				return set_err(WM_EINVAL, "job %d: the CIGAR consumes %lld query / %lld target bases, more than seqs holds behind its offsets", i, (long long)qlen, (long long)tlen);
-			d.q_base = s.q_off; d.t_base = s.t_off;
-		}
-		if (cols >= long_min) {
-			const int nt = (int)((cols + tile_cols - 1) / tile_cols);
-			if (tmap.size() + (size_t)nt >= ((size_t)1 << 28)) return set_err(WM_ENOMEM, "batch holds more than 2^28 tiles; split it");
-			d.tile0 = (int32_t)tmap.size();
-			for (int t = 0; t < nt; ++t) tmap.push_back(make_int2(i, t));
-			lmap.push_back(make_int2(i, nt));
-		} else order.push_back(i);
-	}
-	const size_t n_short = order.size(), n_tiles = tmap.size(), n_long = lmap.size();
-	wm_extra_djob_t *d_jobs = (wm_extra_djob_t*)arena_take(c, nj * sizeof(wm_extra_djob_t));
+		*qlen_out = qlen; *tlen_out = tlen; *cols_out = cols;
+		return 0;
+	};
+	FinalPlan plan;
+	if (const int rc = final_plan(final_view(c), n_jobs, jobs, seqs_bytes, pos, cigars, n_ops, 2, long_min, tile_cols, set_err, measure, plan)) return rc;
+	const size_t n_short = plan.order.size(), n_tiles = plan.tmap.size(), n_long = plan.lmap.size();
 	wm_cs_res_t *d_res = (wm_cs_res_t*)arena_take(c, nj * sizeof(wm_cs_res_t));
 	int *d_cnt = (int*)arena_take(c, (nj + 16) * 4);
 	int *d_total = (int*)arena_take(c, 64);
-	uint32_t *d_cig = (uint32_t*)arena_take(c, (n_ops + 16) * 4);
-	int *d_pre = (int*)arena_take(c, 4 * (n_pre + 16) * 4);
-	int *d_order = (int*)arena_take(c, (n_short + 16) * 4);
-	int2 *d_tmap = (int2*)arena_take(c, (n_tiles + n_long + 16) * sizeof(int2));
 	int *d_part = (int*)arena_take(c, (n_tiles + 1) * 4 * 4);
-	uint8_t *d_seqs = pos ? 0 : (uint8_t*)arena_take(c, seqs_bytes + 64);
-	if (!d_jobs || !d_res || !d_cnt || !d_total || !d_cig || !d_pre || !d_order || !d_tmap || !d_part || (!pos && !d_seqs))
+	FinalDev V;
+	const int staged = d_res && d_cnt && d_total && d_part ? final_stage(c, plan, cigars, n_ops, seqs, seqs_bytes, pos, 4, &V) : WM_ENOMEM;
+	if (staged == WM_ENOMEM)
 		return set_err(WM_ENOMEM, "cs batch (%zu ops, %zu tiles, %zu sequence bytes) does not fit the arena of %.1f MB; split it", n_ops, n_tiles, pos ? (size_t)0 : seqs_bytes, c->arena_bytes / 1048576.0);
-	HIPCHK(hipMemcpyAsync(d_jobs, dj.data(), nj * sizeof(wm_extra_djob_t), hipMemcpyHostToDevice, c->stream));
-	if (n_ops) HIPCHK(hipMemcpyAsync(d_cig, cigars, n_ops * 4, hipMemcpyHostToDevice, c->stream));
-	if (n_short) HIPCHK(hipMemcpyAsync(d_order, order.data(), n_short * 4, hipMemcpyHostToDevice, c->stream));
-	if (n_tiles) HIPCHK(hipMemcpyAsync(d_tmap, tmap.data(), n_tiles * sizeof(int2), hipMemcpyHostToDevice, c->stream));
-	if (n_long) HIPCHK(hipMemcpyAsync(d_tmap + n_tiles, lmap.data(), n_long * sizeof(int2), hipMemcpyHostToDevice, c->stream));
-	if (!pos && seqs_bytes) {
-		HIPCHK(hipMemcpyAsync(d_seqs, seqs, seqs_bytes, hipMemcpyHostToDevice, c->stream));
-		HIPCHK(hipMemsetAsync(d_seqs + seqs_bytes, 4, 64, c->stream));
-	}
-	const size_t ps = n_pre + 16;
-	const cs_dev_pre P = { d_cig, d_pre, d_pre + ps, d_pre + 2 * ps, d_pre + 3 * ps };
-	const cs_dev_src D = { d_seqs, c->d_reads, c->d_reads_nm, c->d_S };
+	if (staged) return staged;
+	const wm_extra_djob_t *d_jobs = V.jobs;
+	const size_t ps = V.pre_stride;
+	const cs_dev_pre P = { V.cig, V.pre, V.pre + ps, V.pre + 2 * ps, V.pre + 3 * ps };
+	const final_dev_src D = { V.seqs, c->d_reads, c->d_reads_nm, c->d_S };
 	// ---- count ----
 	hipLaunchKernelGGL(cs_prefix_kernel, dim3(n_jobs), dim3(64), 0, c->stream, d_jobs, P, mode);
 	if (n_short) {
-		if (pos) hipLaunchKernelGGL(cs_short_count_kernel<true>, dim3((unsigned)n_short), dim3(64), 0, c->stream, d_jobs, d_order, D, P, mode, tile_cols, d_cnt);
-		else hipLaunchKernelGGL(cs_short_count_kernel<false>, dim3((unsigned)n_short), dim3(64), 0, c->stream, d_jobs, d_order, D, P, mode, tile_cols, d_cnt);
+		if (pos) hipLaunchKernelGGL(cs_short_count_kernel<true>, dim3((unsigned)n_short), dim3(64), 0, c->stream, d_jobs, V.order, D, P, mode, tile_cols, d_cnt);
+		else hipLaunchKernelGGL(cs_short_count_kernel<false>, dim3((unsigned)n_short), dim3(64), 0, c->stream, d_jobs, V.order, D, P, mode, tile_cols, d_cnt);
 	}
 	if (n_tiles) {
-		if (pos) hipLaunchKernelGGL(cs_tile_count_kernel<true>, dim3((unsigned)n_tiles), dim3(64), 0, c->stream, d_jobs, d_tmap, D, P, mode, tile_cols, d_part);
-		else hipLaunchKernelGGL(cs_tile_count_kernel<false>, dim3((unsigned)n_tiles), dim3(64), 0, c->stream, d_jobs, d_tmap, D, P, mode, tile_cols, d_part);
-		hipLaunchKernelGGL(cs_combine_kernel, dim3((unsigned)n_long), dim3(64), 0, c->stream, d_jobs, d_tmap + n_tiles, d_part, d_cnt);
+		if (pos) hipLaunchKernelGGL(cs_tile_count_kernel<true>, dim3((unsigned)n_tiles), dim3(64), 0, c->stream, d_jobs, V.tmap, D, P, mode, tile_cols, d_part);
+		else hipLaunchKernelGGL(cs_tile_count_kernel<false>, dim3((unsigned)n_tiles), dim3(64), 0, c->stream, d_jobs, V.tmap, D, P, mode, tile_cols, d_part);
+		hipLaunchKernelGGL(cs_combine_kernel, dim3((unsigned)n_long), dim3(64), 0, c->stream, d_jobs, V.lmap, d_part, d_cnt);
 	}
 	hipLaunchKernelGGL(cs_job_scan_kernel, dim3(1), dim3(64), 0, c->stream, d_cnt, n_jobs, d_res, d_total);
 	HIPCHK(hipGetLastError());
@@ -222,12 +154,12 @@ try {
 	uint8_t *d_out = (uint8_t*)arena_take(c, (size_t)total + 64);
 	if (!d_out) return set_err(WM_ENOMEM, "cs batch (%llu bytes out) does not fit the arena of %.1f MB; split it", (unsigned long long)total, c->arena_bytes / 1048576.0);
 	if (n_short) {
-		if (pos) hipLaunchKernelGGL(cs_short_write_kernel<true>, dim3((unsigned)n_short), dim3(64), 0, c->stream, d_jobs, d_order, D, P, mode, tile_cols, d_res, d_out);
-		else hipLaunchKernelGGL(cs_short_write_kernel<false>, dim3((unsigned)n_short), dim3(64), 0, c->stream, d_jobs, d_order, D, P, mode, tile_cols, d_res, d_out);
+		if (pos) hipLaunchKernelGGL(cs_short_write_kernel<true>, dim3((unsigned)n_short), dim3(64), 0, c->stream, d_jobs, V.order, D, P, mode, tile_cols, d_res, d_out);
+		else hipLaunchKernelGGL(cs_short_write_kernel<false>, dim3((unsigned)n_short), dim3(64), 0, c->stream, d_jobs, V.order, D, P, mode, tile_cols, d_res, d_out);
 	}
 	if (n_tiles) {
-		if (pos) hipLaunchKernelGGL(cs_tile_write_kernel<true>, dim3((unsigned)n_tiles), dim3(64), 0, c->stream, d_jobs, d_tmap, D, P, mode, tile_cols, d_part, d_res, d_out);
-		else hipLaunchKernelGGL(cs_tile_write_kernel<false>, dim3((unsigned)n_tiles), dim3(64), 0, c->stream, d_jobs, d_tmap, D, P, mode, tile_cols, d_part, d_res, d_out);
+		if (pos) hipLaunchKernelGGL(cs_tile_write_kernel<true>, dim3((unsigned)n_tiles), dim3(64), 0, c->stream, d_jobs, V.tmap, D, P, mode, tile_cols, d_part, d_res, d_out);
+		else hipLaunchKernelGGL(cs_tile_write_kernel<false>, dim3((unsigned)n_tiles), dim3(64), 0, c->stream, d_jobs, V.tmap, D, P, mode, tile_cols, d_part, d_res, d_out);
 	}
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(text_out, d_out, (size_t)total, hipMemcpyDeviceToHost, c->stream));

@@ -3,6 +3,7 @@
 // map.c, format.c restated) are compiled in this unit.
 #include "wm_rt.h"
 #include "reads2bit.h"
+#include <optional>
 // ======================================================================================================
 // sketch / seed / chain kernels and their batched entry points
 // ======================================================================================================
@@ -247,28 +248,56 @@ struct GpuOpsCtx {
 		});
 		t_pack += t1 - t0; t_unpack += now_ms() - t2; t_prep += c->t_prep; t_run += c->t_run; t_fetch += c->t_fetch;
 	}
+	// what the four final-CIGAR front ends below put in front of their device call: one position job per request, and the requests' CIGARs end to end in pinned memory
+	struct FinalOps { const uint32_t *ops; size_t n; int32_t t_pos; };
+	struct FinalPack { std::vector<wm_extra_pos_t> jobs; size_t tot = 0; std::optional<UBuf<uint32_t>> cig; };
+	// at(request) = its FinalOps; each(i, ops, n) runs inside the parallel copy, for a front end that has to look at every op; the buffer holds `pools` x (tot + 1) words.
+	// Returns false — nothing done — unless every request is resident. A batch of 2^31 ops or more leaves `error` = too_many and no buffer.
+	template <class R, class At, class Each>
+	bool pack_final(std::vector<R*> &reqs, const char *too_many, const char *site, size_t pools, At at, Each each, FinalPack &P)
+	{
+		const int n = (int)reqs.size();
+		if (!resident) return false;
+		for (int i = 0; i < n; ++i) if (!reqs[i]->resident()) return false;
+		P.jobs.resize(n);
+		for (int i = 0; i < n; ++i) {
+			const R &r = *reqs[i];
+			const FinalOps o = at(r);
+			wm_extra_pos_t &j = P.jobs[i];
+			j.qwin_off = r.qwin_off; j.qwin_len = r.qwin_len; j.q_pos = r.q_pos; j.rid = r.rid; j.t_pos = o.t_pos; j.cig_off = (uint32_t)P.tot; j.n_cigar = (int32_t)o.n;
+			P.tot += o.n;
+		}
+		if (P.tot >= ((size_t)1 << 31)) { error = too_many; return true; }
+		P.cig.emplace(pools * (P.tot + 1), c);
+		WM_SITE(site);
+		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) {
+			const FinalOps o = at(*reqs[i]);
+			if (!o.n) return;
+			memcpy(P.cig->data() + P.jobs[i].cig_off, o.ops, o.n * 4);
+			each(i, o.ops, o.n);
+		});
+		return true;
+	}
+	static void no_each(size_t, const uint32_t*, size_t) {}
+	// call(pool, cap, &used) — and once more at the size it reported, should it report WM_ENOMEM for the pool
+	template <class T, class Call> static int call_retry(std::vector<T> &pool, size_t &used, Call call)
+	{
+		const size_t cap = pool.size();
+		int rc = call(pool.data(), cap, &used);
+		if (rc == WM_ENOMEM && used > cap) { const size_t need = used; pool.resize(need); rc = call(pool.data(), need, &used); }
+		return rc;
+	}
 	// the deferred final scans of regions (mm_update_extra's walk, src/align.c:240-286) through wm_extra_batch_pos: operands as positions in the resident reads and
 	// the uploaded reference, nothing but the CIGARs is shipped. Returns false — nothing done — unless every request is resident (the caller then walks on the host).
 	bool extra_batch(const wm_extra_score_t &sc, std::vector<wm::ExtraReq*> &reqs)
 	{
 		const int n = (int)reqs.size();
-		if (!resident) return false;
-		for (int i = 0; i < n; ++i) if (!reqs[i]->resident()) return false;
 		const double t0 = now_ms();
-		std::vector<wm_extra_pos_t> jobs(n);
-		size_t tot = 0;
-		for (int i = 0; i < n; ++i) {
-			const wm::ExtraReq &r = *reqs[i];
-			wm_extra_pos_t &j = jobs[i];
-			j.qwin_off = r.qwin_off; j.qwin_len = r.qwin_len; j.q_pos = r.q_pos; j.rid = r.rid; j.t_pos = r.t_pos; j.cig_off = (uint32_t)tot; j.n_cigar = r.n_cigar;
-			tot += (size_t)r.n_cigar;
-		}
-		if (tot >= ((size_t)1 << 31)) { error = "extra batch exceeds 2^31 CIGAR ops"; return true; }
-		UBuf<uint32_t> cig(tot + 1, c);
-		WM_SITE("extra.cigars");
-		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) { if (reqs[i]->n_cigar) memcpy(cig.data() + jobs[i].cig_off, reqs[i]->cigar, (size_t)reqs[i]->n_cigar * 4); });
+		FinalPack P;
+		if (!pack_final(reqs, "extra batch exceeds 2^31 CIGAR ops", "extra.cigars", 1, [](const wm::ExtraReq &r) { return FinalOps{ r.cigar, (size_t)r.n_cigar, r.t_pos }; }, no_each, P)) return false;
+		if (!P.cig) return true;
 		std::vector<wm_extra_res_t> res(n);
-		if (wm_extra_batch_pos(c, &sc, n, jobs.data(), cig.data(), tot, res.data())) { fail("extra"); return true; }
+		if (wm_extra_batch_pos(c, &sc, n, P.jobs.data(), P.cig->data(), P.tot, res.data())) { fail("extra"); return true; }
 		uint64_t cols = 0;
 		for (int i = 0; i < n; ++i) {
 			static_assert(sizeof(wm_extra_res_t) == sizeof(wm_extra_t), "wm_extra_res_t is wm_extra_t");
@@ -288,34 +317,22 @@ struct GpuOpsCtx {
 	bool fix_extra_batch(const wm_extra_score_t &sc, std::vector<wm::FixReq*> &reqs)
 	{
 		const int n = (int)reqs.size();
-		if (!resident) return false;
-		for (int i = 0; i < n; ++i) if (!reqs[i]->resident()) return false;
 		const double t0 = now_ms();
-		std::vector<wm_extra_pos_t> jobs(n);
-		size_t tot = 0;
-		for (int i = 0; i < n; ++i) {
-			const wm::FixReq &r = *reqs[i];
-			wm_extra_pos_t &j = jobs[i];
-			j.qwin_off = r.qwin_off; j.qwin_len = r.qwin_len; j.q_pos = r.q_pos; j.rid = r.rid; j.t_pos = r.t_pos; j.cig_off = (uint32_t)tot; j.n_cigar = (int32_t)r.cigar->size();
-			tot += r.cigar->size();
-		}
-		if (tot >= ((size_t)1 << 31)) { error = "fix batch exceeds 2^31 CIGAR ops"; return true; }
-		UBuf<uint32_t> cig(2 * (tot + 1), c);
-		uint32_t *cig_out = cig.data() + tot + 1;
+		FinalPack P;
 		std::atomic<int> refusable(0);
-		WM_SITE("fix.cigars");
-		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) {
-			const std::vector<uint32_t> &cg = *reqs[i]->cigar;
-			if (cg.empty()) return;
-			memcpy(cig.data() + jobs[i].cig_off, cg.data(), cg.size() * 4);
+		if (!pack_final(reqs, "fix batch exceeds 2^31 CIGAR ops", "fix.cigars", 2, [](const wm::FixReq &r) { return FinalOps{ r.cigar->data(), r.cigar->size(), r.t_pos }; },
+		                [&](size_t, const uint32_t *cg, size_t nc) {
 			uint32_t bad = 0;
-			for (size_t k = 0; k < cg.size(); ++k) bad |= (uint32_t)(cg[k] - 3u < 13u);          // (length 0 and code >= 3: the word is 3 .. 15)
+			for (size_t k = 0; k < nc; ++k) bad |= (uint32_t)(cg[k] - 3u < 13u);          // (length 0 and code >= 3: the word is 3 .. 15)
 			if (bad) refusable = 1;
-		});
+		}, P)) return false;
+		if (!P.cig) return true;
 		if (refusable.load()) return false;
+		const std::vector<wm_extra_pos_t> &jobs = P.jobs;
+		uint32_t *cig_out = P.cig->data() + P.tot + 1;
 		std::vector<wm_extra_res_t> res(n);
 		std::vector<wm_fix_res_t> fr(n);
-		if (wm_fix_extra_batch_pos(c, &sc, n, jobs.data(), cig.data(), tot, cig_out, fr.data(), res.data())) { fail("fix"); return true; }
+		if (wm_fix_extra_batch_pos(c, &sc, n, jobs.data(), P.cig->data(), P.tot, cig_out, fr.data(), res.data())) { fail("fix"); return true; }
 		WM_SITE("fix.unpack");
 		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) {
 			wm::FixReq &r = *reqs[i];
@@ -337,28 +354,15 @@ struct GpuOpsCtx {
 	bool eqx_batch(std::vector<wm::EqxReq*> &reqs)
 	{
 		const int n = (int)reqs.size();
-		if (!resident) return false;
-		for (int i = 0; i < n; ++i) if (!reqs[i]->resident()) return false;
 		const double t0 = now_ms();
-		std::vector<wm_extra_pos_t> jobs(n);
-		size_t tot = 0, cap = 16;
-		for (int i = 0; i < n; ++i) {
-			const wm::EqxReq &r = *reqs[i];
-			wm_extra_pos_t &j = jobs[i];
-			j.qwin_off = r.qwin_off; j.qwin_len = r.qwin_len; j.q_pos = r.q_pos; j.rid = r.rid; j.t_pos = r.t_pos; j.cig_off = (uint32_t)tot; j.n_cigar = (int32_t)r.cigar->size();
-			tot += r.cigar->size();
-			cap += (size_t)std::max<int32_t>(r.cap_hint, (int32_t)std::min<size_t>(r.cigar->size(), INT32_MAX));
-		}
-		if (tot >= ((size_t)1 << 31)) { error = "eqx batch exceeds 2^31 CIGAR ops"; return true; }
-		UBuf<uint32_t> cig(tot + 1, c);
-		WM_SITE("eqx.cigars");
-		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) { if (!reqs[i]->cigar->empty()) memcpy(cig.data() + jobs[i].cig_off, reqs[i]->cigar->data(), reqs[i]->cigar->size() * 4); });
+		FinalPack P;
+		if (!pack_final(reqs, "eqx batch exceeds 2^31 CIGAR ops", "eqx.cigars", 1, [](const wm::EqxReq &r) { return FinalOps{ r.cigar->data(), r.cigar->size(), r.t_pos }; }, no_each, P)) return false;
+		if (!P.cig) return true;
+		size_t cap = 16, used = 0;
+		for (int i = 0; i < n; ++i) cap += (size_t)std::max<int32_t>(reqs[i]->cap_hint, (int32_t)std::min<size_t>(reqs[i]->cigar->size(), INT32_MAX));
 		std::vector<wm_eqx_res_t> res(n);
 		std::vector<uint32_t> pool(cap);
-		size_t used = 0;
-		int rc = wm_eqx_batch_pos(c, n, jobs.data(), cig.data(), tot, pool.data(), cap, &used, res.data());
-		if (rc == WM_ENOMEM && used > cap) { cap = used; pool.resize(cap); rc = wm_eqx_batch_pos(c, n, jobs.data(), cig.data(), tot, pool.data(), cap, &used, res.data()); }
-		if (rc) { fail("eqx"); return true; }
+		if (call_retry(pool, used, [&](uint32_t *out, size_t out_cap, size_t *out_used) { return wm_eqx_batch_pos(c, n, P.jobs.data(), P.cig->data(), P.tot, out, out_cap, out_used, res.data()); })) { fail("eqx"); return true; }
 		WM_SITE("eqx.unpack");
 		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) {
 			wm::EqxReq &r = *reqs[i];
@@ -388,24 +392,13 @@ struct GpuOpsCtx {
 			bound += (uint64_t)b;
 		}
 		const double t0 = now_ms();
-		std::vector<wm_extra_pos_t> jobs(n);
-		size_t tot = 0;
-		for (int i = 0; i < n; ++i) {
-			const wm::CsReq &r = *reqs[i];
-			wm_extra_pos_t &j = jobs[i];
-			j.qwin_off = r.qwin_off; j.qwin_len = r.qwin_len; j.q_pos = r.q_pos; j.rid = r.rid; j.t_pos = r.rs; j.cig_off = (uint32_t)tot; j.n_cigar = (int32_t)r.cigar->size();
-			tot += r.cigar->size();
-		}
-		if (tot >= ((size_t)1 << 31)) { error = "cs batch exceeds 2^31 CIGAR ops"; return true; }
-		UBuf<uint32_t> cig(tot + 1, c);
-		WM_SITE("cs.cigars");
-		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) { if (!reqs[i]->cigar->empty()) memcpy(cig.data() + jobs[i].cig_off, reqs[i]->cigar->data(), reqs[i]->cigar->size() * 4); });
+		FinalPack P;
+		if (!pack_final(reqs, "cs batch exceeds 2^31 CIGAR ops", "cs.cigars", 1, [](const wm::CsReq &r) { return FinalOps{ r.cigar->data(), r.cigar->size(), r.rs }; }, no_each, P)) return false;
+		if (!P.cig) return true;
 		std::vector<wm_cs_res_t> res(n);
-		size_t cap = (size_t)(bound / 8) + 64, used = 0;
-		std::vector<char> pool(cap);
-		int rc = wm_cs_batch_pos(c, mode, n, jobs.data(), cig.data(), tot, pool.data(), cap, &used, res.data());
-		if (rc == WM_ENOMEM && used > cap) { cap = used; pool.resize(cap); rc = wm_cs_batch_pos(c, mode, n, jobs.data(), cig.data(), tot, pool.data(), cap, &used, res.data()); }
-		if (rc) { fail("cs"); return true; }
+		size_t used = 0;
+		std::vector<char> pool((size_t)(bound / 8) + 64);
+		if (call_retry(pool, used, [&](char *out, size_t out_cap, size_t *out_used) { return wm_cs_batch_pos(c, mode, n, P.jobs.data(), P.cig->data(), P.tot, out, out_cap, out_used, res.data()); })) { fail("cs"); return true; }
 		WM_SITE("cs.unpack");
 		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) { reqs[i]->body->assign(pool.data() + res[i].off, (size_t)res[i].len); });
 		wm::CsStats &st = wm::cs_stats();

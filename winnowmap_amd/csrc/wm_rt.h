@@ -1,11 +1,12 @@
 // wm_rt.h — what the translation units of libwmgpu.so share (NOT part of the C-ABI: include/wm_gpu.h is). Round 6: the library was one
 // 3 900-line translation unit; it is six now —
-//   wm_rt.hip      runtime: errors, device contexts, arena, pinned slab, process-wide defaults
+//   wm_rt.hip      runtime: errors, device contexts, arena, pinned slab, process-wide defaults; final_stage, the staging step of the three final-CIGAR units
 //   wm_ksw.hip     the alignment kernels' entry points, routing, batch planning / launch / fetch (ksw2: src/ksw2_extd2_sse.c, src/ksw2_exts2_sse.c)
-//   wm_extra.hip   the scan of mm_update_extra over batches of final CIGARs (src/align.c:240-286): entry points, validation, class split, launches
-//   wm_cs.hip      the bodies of the cs:Z / MD:Z tags over batches of final CIGARs (src/format.c:141-218): entry points, validation, class split, the two passes
-//   wm_eqx.hip     mm_update_cigar_eqx over batches of final CIGARs (src/align.c:169-238): entry points, validation, class split, the two passes
+//   wm_extra.hip   the scan of mm_update_extra over batches of final CIGARs (src/align.c:240-286): entry points, what the pass measures and refuses, launches
 //                  ... and mm_fix_cigar in front of it (src/align.c:91-167; fix_kernel.h): wm_fix_extra_batch / wm_fix_extra_batch_pos
+//   wm_cs.hip      the bodies of the cs:Z / MD:Z tags over batches of final CIGARs (src/format.c:141-218): entry points, what the pass measures and refuses, the two passes
+//   wm_eqx.hip     mm_update_cigar_eqx over batches of final CIGARs (src/align.c:169-238): entry points, what the pass measures and refuses, the two passes
+//                  (the three share one batch planner — validation, job records, class split: host/wm_final_plan.h, host only —, final_stage, and final_src.h)
 //   wm_index.hip   sketch / seed / chain batch operations, the index on the device, the -W counter (src/sketch.c, src/index.c, src/map.c:97-254, src/chain.c)
 //   wm_window.hip  the fused window call (sketch -> seed -> sort -> chain -> extraction)
 //   wm_mapper.hip  the mapper: device contexts as a pool, mapping calls, file loops, statistics; the host sources (host/*.cpp) are compiled here
@@ -30,6 +31,7 @@
 #include <unistd.h>
 #include "host/wm_core.h"
 #include "host/wm_index.h"
+#include "host/wm_final_plan.h"
 #include "wm_internal.h"
 #include "ksw_plan.h"
 // large staging buffers: no value-initialisation (a std::vector would memset hundreds of MB per batch). When a context is
@@ -129,6 +131,15 @@ void *arena_take(wm_ctx_t *c, size_t bytes);
 // releases what a batched call took from the arena when the call returns
 struct ArenaMark { wm_ctx_t *c; size_t m; ArenaMark(wm_ctx_t *c_) : c(c_), m(c_->arena_used) {} ~ArenaMark() { c->arena_used = m; } };
 int reads_alloc(wm_ctx_t *c, size_t cap);
+
+// the final-CIGAR calls (wm_extra.hip, wm_eqx.hip, wm_cs.hip): host/wm_final_plan.h plans a batch, final_stage puts the plan on the device, the unit launches its pass
+int extra_long_min_cols();          // wm_extra.hip: the values of wm_extra_set_routing route all three (wm_extra_tile_cols is in the C-ABI)
+static_assert(sizeof(wm_final_pair) == sizeof(int2), "the planner's pairs are the kernels' int2");
+inline FinalView final_view(const wm_ctx_t *c) { return { c->reads_bytes, c->seq_len.data(), c->seq_off.data(), c->seq_len.size() }; }
+// pre: n_pre_arrays arrays of pre_stride = n_pre + 16 ints; lmap follows tmap; seqs (byte form only) ends in 64 bytes of code 4
+struct FinalDev { wm_extra_djob_t *jobs; uint32_t *cig; int *pre; size_t pre_stride; int *order; int2 *tmap, *lmap; uint8_t *seqs; };
+// takes these from the arena and queues their uploads on the context's stream. WM_ENOMEM, without a message and with nothing queued, if the arena cannot hold them
+int final_stage(wm_ctx_t *c, const FinalPlan &plan, const uint32_t *cigars, size_t n_ops, const uint8_t *seqs, size_t seqs_bytes, const wm_extra_pos_t *pos, int n_pre_arrays, FinalDev *dev);
 
 struct wm_index_s { wm::Index ix; };
 

@@ -1,4 +1,5 @@
-// wm_rt.hip — libwmgpu.so, runtime unit: errors, device contexts (stream + arena + pinned slab + events), process-wide defaults. No kernels here.
+// wm_rt.hip — libwmgpu.so, runtime unit: errors, device contexts (stream + arena + pinned slab + events), process-wide defaults, the staging step of the
+// final-CIGAR calls. No kernels here.
 // There is no CPU compute path in this library: every entry point needs a HIP device (wm_ctx_create fails with WM_ENODEV without one).
 #include "wm_rt.h"
 
@@ -202,4 +203,29 @@ void *arena_take(wm_ctx_t *c, size_t bytes)
 	return c->arena + a;
 }
 
+// the staging step of the final-CIGAR calls (wm_extra.hip, wm_eqx.hip, wm_cs.hip): what every pass reads, from the arena and onto the call's stream
+int final_stage(wm_ctx_t *c, const FinalPlan &plan, const uint32_t *cigars, size_t n_ops, const uint8_t *seqs, size_t seqs_bytes, const wm_extra_pos_t *pos, int n_pre_arrays, FinalDev *dev)
+{
+	const size_t nj = plan.dj.size(), n_short = plan.order.size(), n_tiles = plan.tmap.size(), n_long = plan.lmap.size();
+	FinalDev &D = *dev;
+	D.jobs = (wm_extra_djob_t*)arena_take(c, nj * sizeof(wm_extra_djob_t));
+	D.cig = (uint32_t*)arena_take(c, (n_ops + 16) * 4);
+	D.pre_stride = plan.n_pre + 16;
+	D.pre = (int*)arena_take(c, (size_t)n_pre_arrays * D.pre_stride * 4);
+	D.order = (int*)arena_take(c, (n_short + 16) * 4);
+	D.tmap = (int2*)arena_take(c, (n_tiles + n_long + 16) * sizeof(int2));
+	D.seqs = pos ? 0 : (uint8_t*)arena_take(c, seqs_bytes + 64);          // (+ slack: the word-wise gap scan reads to the end of the word that holds the last base)
+	if (!D.jobs || !D.cig || !D.pre || !D.order || !D.tmap || (!pos && !D.seqs)) return WM_ENOMEM;
+	D.lmap = D.tmap + n_tiles;
+	HIPCHK(hipMemcpyAsync(D.jobs, plan.dj.data(), nj * sizeof(wm_extra_djob_t), hipMemcpyHostToDevice, c->stream));
+	if (n_ops) HIPCHK(hipMemcpyAsync(D.cig, cigars, n_ops * 4, hipMemcpyHostToDevice, c->stream));
+	if (n_short) HIPCHK(hipMemcpyAsync(D.order, plan.order.data(), n_short * 4, hipMemcpyHostToDevice, c->stream));
+	if (n_tiles) HIPCHK(hipMemcpyAsync(D.tmap, plan.tmap.data(), n_tiles * sizeof(int2), hipMemcpyHostToDevice, c->stream));
+	if (n_long) HIPCHK(hipMemcpyAsync(D.lmap, plan.lmap.data(), n_long * sizeof(int2), hipMemcpyHostToDevice, c->stream));
+	if (!pos && seqs_bytes) {
+		HIPCHK(hipMemcpyAsync(D.seqs, seqs, seqs_bytes, hipMemcpyHostToDevice, c->stream));
+		HIPCHK(hipMemsetAsync(D.seqs + seqs_bytes, 4, 64, c->stream));
+	}
+	return WM_OK;
+}
 
