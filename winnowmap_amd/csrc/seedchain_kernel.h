@@ -49,14 +49,97 @@ WM_DEV vbool seed_skip(const wm_index_view_t &ix, int flag, uint32_t q_lo, int q
 	return skip;
 }
 
+// What collect_seed_hits knows about the query of one job, whichever job type carries it (wm_seed_job_t, wm_win_job_t): filt = the flag bits skip_seed has something
+// to do for (wave-uniform; 0 on the default path), the name key, the length of the sequence that is seeded, mid_occ. Passed by value: five scalar registers.
+struct seed_query_t { int filt; uint32_t q_lo; int q_eq, qlen, max_occ; };
+WM_DEV seed_query_t seed_query(int flag, uint32_t q_lo, int q_eq, int qlen, int max_occ) { return { flag & (0x100000 | 0x200000 | 3), q_lo, q_eq, qlen, max_occ }; }
+
+// mm_idx_get (src/index.c:88-105) for the lanes that hold a minimizer (the caller's WM_IF): the open-addressing probe of the flat index, key -> (cnt, first).
+// Both stay as they are (0) for a key the index does not hold.
+WM_DEV void seed_probe(const wm_index_view_t &ix, const V<uint64_t> mx, V<int> &cnt, V<uint64_t> &first)
+{
+	const uint64_t hmask = ((uint64_t)1 << ix.hbits) - 1;
+	const V<uint64_t> key = mx >> 8;
+	V<uint64_t> s = (key * (uint64_t)0x9E3779B97F4A7C15ULL) >> (64 - ix.hbits);
+	vbool probing = s == s;                          // true
+	for (int guard = 0; guard < (1 << 20) && any(probing); ++guard) {
+		WM_IF(probing)
+			V<uint64_t> hk = gld(ix.hkey, s);
+			WM_IF(hk == key)
+				V<uint64_t> hv = gld(ix.hval, s);
+				cnt = cast<int>(hv & (uint64_t)0xffffffffu); first = hv >> 32;
+			WM_END
+			probing = (hk != key) && (hk != ~(uint64_t)0);
+			s = (s + (uint64_t)1) & hmask;
+		WM_END
+	}
+}
+
+// how many anchors a minimizer contributes: its occurrences if they pass the occurrence filter (src/map.c:108-117) and, when the filter bits are set, those of
+// them that skip_seed keeps (src/map.c:237) — counted before the expansion so that the anchors of a job can be placed with one prefix sum (and one atomic)
+WM_DEV V<int> seed_kept(const wm_index_view_t &ix, const seed_query_t q, const vbool have, const V<int> cnt, const V<uint64_t> first, const V<uint64_t> my)
+{
+	V<int> emit = sel(have && cnt < q.max_occ, cnt, 0);
+	WM_IF(q.filt != 0 && emit > 0)
+		V<int> kept = 0;
+		for (int h = 0; h < q.max_occ && any(emit > h); ++h)
+			WM_IF(emit > h)
+				vbool self = emit != emit;
+				kept = kept + sel(seed_skip(ix, q.filt, q.q_lo, q.q_eq, q.qlen, gld(ix.P, first + (uint64_t)h), cast<uint32_t>(my), self), 0, 1);
+			WM_END
+		emit = kept;
+	WM_END
+	return emit;
+}
+
+// The expansion of one tile of 64 minimizers (src/map.c:232-249): lane l holds minimizer m = (mx, my) of the job's list mini[0 .. n_mini) with its probe result
+// (cnt, first) and its kept count emit; the tile's anchors go to out[2 w ..), w = base + the exclusive prefix sum of emit, in minimizer order — with the tandem
+// bit (:121-122), the strand flip, MM_SEED_SELF and skip_seed. BOUNDED: only the slots w < cap are written (a slot sized by a guess, the caller retries);
+// otherwise the region was allocated for exactly these anchors and the stores are unconditional. Returns the tile's anchor count (uniform).
+template <bool BOUNDED>
+WM_DEV int seed_expand_tile(const wm_index_view_t &ix, const seed_query_t q, const uint64_t *mini, int n_mini, const V<int> m, const V<uint64_t> mx, const V<uint64_t> my,
+                            const V<int> cnt, const V<uint64_t> first, const V<int> emit, int base, uint64_t *out, int cap)
+{
+	const V<int> incl = wave_scan_add(emit);
+	WM_IF(emit > 0)
+		const V<uint32_t> q_pos = cast<uint32_t>(my), q_span = cast<uint32_t>(mx & (uint64_t)0xff);
+		// tandem: the neighbouring minimizer (in the whole list) has the same key (src/map.c:121-122)
+		vbool tandem = q_pos != q_pos;               // false
+		WM_IF(m > 0) tandem = tandem || ((gld(mini, (m - 1) * 2) >> 8) == (mx >> 8)); WM_END
+		WM_IF(m < n_mini - 1) tandem = tandem || ((gld(mini, (m + 1) * 2) >> 8) == (mx >> 8)); WM_END
+		V<int> w = incl - emit + base;
+		for (int h = 0; h < q.max_occ && any(cnt > h); ++h)
+			WM_IF(cnt > h)
+				const V<uint64_t> r = gld(ix.P, first + (uint64_t)h);
+				const V<uint64_t> rpos = (r & (uint64_t)0xffffffffu) >> 1;
+				const vbool fwd = cast<uint32_t>(r & (uint64_t)1) == (q_pos & 1u);
+				vbool keep = rpos == rpos, self = rpos != rpos;
+				if (q.filt) keep = !seed_skip(ix, q.filt, q.q_lo, q.q_eq, q.qlen, r, q_pos, self);
+				WM_IF(keep)
+					V<uint64_t> ax = (r & (uint64_t)0xffffffff00000000ULL) | rpos;
+					V<uint64_t> ay = cast<uint64_t>(q_span) << 32;
+					WM_IF(fwd) ay = ay | cast<uint64_t>(q_pos >> 1); WM_ELSE
+						ax = ax | ((uint64_t)1 << 63);
+						ay = ay | cast<uint64_t>(cast<uint32_t>(V<int>(q.qlen) - cast<int>((q_pos >> 1) + 1u - q_span) - 1));
+					WM_END
+					ay = sel(tandem, ay | ((uint64_t)1 << 42), ay);
+					if (q.filt & 1) ay = sel(self, ay | ((uint64_t)1 << 43), ay);      // MM_SEED_SELF (src/map.c:247)
+					if (BOUNDED) { WM_IF(w < cap) gst(out, w * 2, ax); gst(out, w * 2 + 1, ay); WM_END }
+					else { gst(out, w * 2, ax); gst(out, w * 2 + 1, ay); }
+					w = w + 1;
+				WM_END
+			WM_END
+	WM_END
+	return readlane(incl, 63);
+}
+
 WM_DEV void seed_wave(const wm_index_view_t ix, const wm_seed_job_t jb, const wm128_t *mini_pool, wm128_t *anchor_pool,
                       int *occ_scratch /* n_mini ints */, wm_seed_res_t *res, uint32_t *first_scratch = 0 /* n_mini: every minimizer's first position, kept for the heap order (MM_F_HEAP_SORT) */)
 {
 	const V<int> ln = lane();
 	const uint64_t *mini = (const uint64_t*)(mini_pool + jb.mini_off);
 	uint64_t *outp = (uint64_t*)(anchor_pool + jb.out_off);
-	const uint64_t hmask = ((uint64_t)1 << ix.hbits) - 1;
-	const int filt = jb.flag & (0x100000 | 0x200000 | 3);     // skip_seed has something to do (wave-uniform; 0 on the default path)
+	const seed_query_t q = seed_query(jb.flag, jb.q_lo, jb.q_eq, jb.qlen, jb.max_occ);
 	int base = 0;                                        // anchors written so far
 	for (int m0 = 0; m0 < jb.n_mini; m0 += 64) {
 		const V<int> m = ln + m0;
@@ -65,68 +148,11 @@ WM_DEV void seed_wave(const wm_index_view_t ix, const wm_seed_job_t jb, const wm
 		V<int> cnt = 0;
 		WM_IF(have)
 			mx = gld(mini, m * 2); my = gld(mini, m * 2 + 1);
-			const V<uint64_t> key = mx >> 8;
-			V<uint64_t> s = (key * (uint64_t)0x9E3779B97F4A7C15ULL) >> (64 - ix.hbits);
-			vbool probing = s == s;                      // true
-			for (int guard = 0; guard < (1 << 20) && any(probing); ++guard) {
-				WM_IF(probing)
-					V<uint64_t> hk = gld(ix.hkey, s);
-					WM_IF(hk == key)
-						V<uint64_t> hv = gld(ix.hval, s);
-						cnt = cast<int>(hv & (uint64_t)0xffffffffu); first = hv >> 32;
-					WM_END
-					probing = (hk != key) && (hk != ~(uint64_t)0);
-					s = (s + (uint64_t)1) & hmask;
-				WM_END
-			}
+			seed_probe(ix, mx, cnt, first);
 			cst(occ_scratch, m, cnt);
 			if (first_scratch) gst(first_scratch, m, cast<uint32_t>(first));
 		WM_END
-		// occurrence filter + (optional) strand filter decide how many anchors each minimizer contributes
-		V<int> emit = sel(have && cnt < jb.max_occ, cnt, 0);
-		WM_IF(filt != 0 && emit > 0)
-			V<int> kept = 0;
-			for (int h = 0; h < jb.max_occ && any(emit > h); ++h)
-				WM_IF(emit > h)
-					vbool self = emit != emit;
-					kept = kept + sel(seed_skip(ix, filt, jb.q_lo, jb.q_eq, jb.qlen, gld(ix.P, first + (uint64_t)h), cast<uint32_t>(my), self), 0, 1);
-				WM_END
-			emit = kept;
-		WM_END
-		// exclusive prefix sum across the tile
-		V<int> incl = emit;
-		for (int o = 1; o < 64; o <<= 1) incl = incl + sel(ln >= o, shr_n(incl, o), 0);
-		const V<int> excl = incl - emit;
-		const int tile_total = readlane(incl, 63);
-		WM_IF(emit > 0)
-			const V<uint32_t> q_pos = cast<uint32_t>(my), q_span = cast<uint32_t>(mx & (uint64_t)0xff);
-			// tandem: the neighbouring minimizer (in the whole list) has the same key (src/map.c:121-122)
-			vbool tandem = q_pos != q_pos;               // false
-			WM_IF(m > 0) tandem = tandem || ((gld(mini, (m - 1) * 2) >> 8) == (mx >> 8)); WM_END
-			WM_IF(m < jb.n_mini - 1) tandem = tandem || ((gld(mini, (m + 1) * 2) >> 8) == (mx >> 8)); WM_END
-			V<int> w = base + excl;
-			for (int h = 0; h < jb.max_occ && any(cnt > h); ++h)
-				WM_IF(cnt > h)
-					const V<uint64_t> r = gld(ix.P, first + (uint64_t)h);
-					const V<uint64_t> rpos = (r & (uint64_t)0xffffffffu) >> 1;
-					const vbool fwd = cast<uint32_t>(r & (uint64_t)1) == (q_pos & 1u);
-					vbool keep = rpos == rpos, self = rpos != rpos;
-					if (filt) keep = !seed_skip(ix, filt, jb.q_lo, jb.q_eq, jb.qlen, r, q_pos, self);
-					WM_IF(keep)
-						V<uint64_t> ax = (r & (uint64_t)0xffffffff00000000ULL) | rpos;
-						V<uint64_t> ay = cast<uint64_t>(q_span) << 32;
-						WM_IF(fwd) ay = ay | cast<uint64_t>(q_pos >> 1); WM_ELSE
-							ax = ax | ((uint64_t)1 << 63);
-							ay = ay | cast<uint64_t>(cast<uint32_t>(V<int>(jb.qlen) - cast<int>((q_pos >> 1) + 1u - q_span) - 1));
-						WM_END
-						ay = sel(tandem, ay | ((uint64_t)1 << 42), ay);
-						if (filt & 1) ay = sel(self, ay | ((uint64_t)1 << 43), ay);      // MM_SEED_SELF
-						WM_IF(w < jb.cap) gst(outp, w * 2, ax); gst(outp, w * 2 + 1, ay); WM_END
-						w = w + 1;
-					WM_END
-				WM_END
-		WM_END
-		base += tile_total;
+		base += seed_expand_tile<true>(ix, q, mini, jb.n_mini, m, mx, my, cnt, first, seed_kept(ix, q, have, cnt, first, my), base, outp, jb.cap);
 	}
 	// rep_len: sequential over the minimizers (src/map.c:111-116,126); uniform code, one result
 	int rep_st = 0, rep_en = 0, rep_len = 0;

@@ -19,6 +19,7 @@
 #ifndef WM_DEV
 #error "include simt.h before window_kernel.h"
 #endif
+#include <type_traits>
 #include "wm_internal.h"
 
 namespace wmk {
@@ -46,8 +47,7 @@ WM_DEV void win_seed_wave(const wm_index_view_t ix, const wm_win_job_t jb, const
 {
 	const V<int> ln = lane();
 	const uint64_t *mini = (const uint64_t*)mini_;
-	const uint64_t hmask = ((uint64_t)1 << ix.hbits) - 1;
-	const int filt = jb.seed_flag & (0x100000 | 0x200000 | 3);         // skip_seed (seedchain_kernel.h) has something to do: wave-uniform, 0 on the default path
+	const seed_query_t q = seed_query(jb.seed_flag, jb.q_lo, jb.q_eq, jb.len, jb.max_occ);      // (seedchain_kernel.h, as the probe, the kept count and the expansion)
 	int total = 0, rep_len = 0, carry_en = 0;
 	for (int m0 = 0; m0 < n_mini; m0 += 64) {
 		const V<int> m = ln + m0;
@@ -56,31 +56,9 @@ WM_DEV void win_seed_wave(const wm_index_view_t ix, const wm_win_job_t jb, const
 		V<int> cnt = 0;
 		WM_IF(have)
 			mx = gld(mini, m * 2); my = gld(mini, m * 2 + 1);
-			const V<uint64_t> key = mx >> 8;
-			V<uint64_t> s = (key * (uint64_t)0x9E3779B97F4A7C15ULL) >> (64 - ix.hbits);
-			vbool probing = s == s;
-			for (int guard = 0; guard < (1 << 20) && any(probing); ++guard) {
-				WM_IF(probing)
-					V<uint64_t> hk = gld(ix.hkey, s);
-					WM_IF(hk == key)
-						V<uint64_t> hv = gld(ix.hval, s);
-						cnt = cast<int>(hv & (uint64_t)0xffffffffu); first = hv >> 32;
-					WM_END
-					probing = (hk != key) && (hk != ~(uint64_t)0);
-					s = (s + (uint64_t)1) & hmask;
-				WM_END
-			}
+			seed_probe(ix, mx, cnt, first);
 		WM_END
-		V<int> emit = sel(have && cnt < jb.max_occ, cnt, 0);
-		WM_IF(filt != 0 && emit > 0)                                       // the occurrences skip_seed keeps (src/map.c:237), so that the wave can take its slots with one atomic
-			V<int> kept = 0;
-			for (int h = 0; h < jb.max_occ && any(emit > h); ++h)
-				WM_IF(emit > h)
-					vbool self = emit != emit;
-					kept = kept + sel(seed_skip(ix, filt, jb.q_lo, jb.q_eq, jb.len, gld(ix.P, first + (uint64_t)h), cast<uint32_t>(my), self), 0, 1);
-				WM_END
-			emit = kept;
-		WM_END
+		const V<int> emit = seed_kept(ix, q, have, cnt, first, my);
 		WM_IF(have) gst(occ, m, cnt); gst(first_, m, cast<uint32_t>(first)); gst(emit_, m, emit); WM_END
 		// rep_len: the dropped minimizers of this tile
 		const vbool dropped = have && cnt >= jb.max_occ;
@@ -115,37 +93,7 @@ WM_DEV void win_seed_wave(const wm_index_view_t ix, const wm_win_job_t jb, const
 		V<int> cnt = 0, emit = 0;
 		V<uint64_t> first = (uint64_t)0, mx = (uint64_t)0, my = (uint64_t)0;
 		WM_IF(have) cnt = gld(occ, m); emit = gld(emit_, m); first = cast<uint64_t>(gld(first_, m)); mx = gld(mini, m * 2); my = gld(mini, m * 2 + 1); WM_END
-		const V<int> incl = wave_scan_add(emit);
-		const V<int> excl = incl - emit;
-		const int tile_total = readlane(incl, 63);
-		WM_IF(emit > 0)
-			const V<uint32_t> q_pos = cast<uint32_t>(my), q_span = cast<uint32_t>(mx & (uint64_t)0xff);
-			vbool tandem = q_pos != q_pos;                // the neighbouring minimizer has the same key (src/map.c:121-122)
-			WM_IF(m > 0) tandem = tandem || ((gld(mini, (m - 1) * 2) >> 8) == (mx >> 8)); WM_END
-			WM_IF(m < n_mini - 1) tandem = tandem || ((gld(mini, (m + 1) * 2) >> 8) == (mx >> 8)); WM_END
-			V<int> w = excl + base;
-			for (int h = 0; h < jb.max_occ && any(cnt > h); ++h)
-				WM_IF(cnt > h)
-					const V<uint64_t> r = gld(ix.P, first + (uint64_t)h);
-					const V<uint64_t> rpos = (r & (uint64_t)0xffffffffu) >> 1;
-					const vbool fwd = cast<uint32_t>(r & (uint64_t)1) == (q_pos & 1u);
-					vbool keep = rpos == rpos, self = rpos != rpos;
-					if (filt) keep = !seed_skip(ix, filt, jb.q_lo, jb.q_eq, jb.len, r, q_pos, self);
-					WM_IF(keep)
-						V<uint64_t> ax = (r & (uint64_t)0xffffffff00000000ULL) | rpos;
-						V<uint64_t> ay = cast<uint64_t>(q_span) << 32;
-						WM_IF(fwd) ay = ay | cast<uint64_t>(q_pos >> 1); WM_ELSE
-							ax = ax | ((uint64_t)1 << 63);
-							ay = ay | cast<uint64_t>(cast<uint32_t>(V<int>(jb.len) - cast<int>((q_pos >> 1) + 1u - q_span) - 1));
-						WM_END
-						ay = sel(tandem, ay | ((uint64_t)1 << 42), ay);
-						if (filt & 1) ay = sel(self, ay | ((uint64_t)1 << 43), ay);      // MM_SEED_SELF (src/map.c:247)
-						gst(outp, w * 2, ax); gst(outp, w * 2 + 1, ay);
-						w = w + 1;
-					WM_END
-				WM_END
-		WM_END
-		base += tile_total;
+		base += seed_expand_tile<false>(ix, q, mini, n_mini, m, mx, my, cnt, first, emit, base, outp, 0);
 	}
 }
 
@@ -606,7 +554,8 @@ template <bool G> WM_DEV void win_extract_wave(int n, int min_cnt, int min_sc, c
 // chaining fill and the extraction — by ONE wavefront without leaving LDS. ga: the job's anchors as the seed kernel wrote them (global).
 // lds: WIN_SMALL_LDS bytes. The results go to the call's result pools like those of win_extract_wave.
 // ------------------------------------------------------------------------------------------------------------------------------
-enum { WIN_SMALL = 256, WIN_WS_PAD = (WIN_WS_INTS + 3) & ~3,
+// WIN_LARGE: the largest job whose sort, extraction and heap order stay in LDS (beyond it: global memory); WIN_NWV: wavefronts of the heap order's workgroup.
+enum { WIN_SMALL = 256, WIN_LARGE = 4096, WIN_NWV = 8, WIN_WS_PAD = (WIN_WS_INTS + 3) & ~3,
        WIN_SMALL_LDS = WIN_WS_PAD * 4 + WIN_SMALL * (16 /* anchors */ + 28 /* fill window */ + 8 /* v, t */ + 8 /* z/u */ + 16 /* b */ + 16 /* w */) };
 WM_DEV void win_small_wave(const wm_win_job_t jb, int n, const wm128_t *ga_, unsigned char *lds, wm_win_res_t *res, uint64_t *u_pool, wm128_t *v_pool, uint64_t *pool_ctr)
 {
@@ -848,6 +797,16 @@ WM_DEV int seed_heap_job(int NWV, const wm_index_view_t ix, const wm_seed_job_t 
 {
 	if (m > jb.cap || m <= lo || m > hi) return 0;                            // (a slot that overflowed is left to the retry)
 	return heap_order_block(NWV, ix, jb.flag & (0x100000 | 0x200000 | 3), jb.q_lo, jb.q_eq, jb.qlen, jb.max_occ, mini, jb.n_mini, occ, first, a, m, b0, b1, hl, hcap, hg, lds);
+}
+
+// The three launches of the heap order over the size m of a job's seeded part: (-1, WIN_SMALL] by one wavefront in LDS, (WIN_SMALL, WIN_LARGE] by WIN_NWV wavefronts
+// in LDS, the rest by WIN_NWV wavefronts in global memory (lds_cap = 0). Host code: the two seeding calls have kernels of their own around win_heap_job / seed_heap_job,
+// launch(integral_constant<NWV>, dynamic LDS bytes, lo, hi, lds_cap) queues one and returns 0 or an error.
+template <class Launch> inline int heap_order_launch(Launch launch)
+{
+	if (const int rc = launch(std::integral_constant<int, 1>(), (size_t)WIN_HEAP_INTS(1) * 4 + (size_t)WIN_SMALL * 32, -1, (int)WIN_SMALL, (int)WIN_SMALL)) return rc;
+	if (const int rc = launch(std::integral_constant<int, WIN_NWV>(), (size_t)WIN_HEAP_INTS(WIN_NWV) * 4 + (size_t)WIN_LARGE * 32, (int)WIN_SMALL, (int)WIN_LARGE, (int)WIN_LARGE)) return rc;
+	return launch(std::integral_constant<int, WIN_NWV>(), (size_t)WIN_HEAP_INTS(WIN_NWV) * 4, (int)WIN_LARGE, 0x7fffffff, 0);
 }
 
 } // namespace wmk

@@ -7,6 +7,7 @@
 #include "sketch_kernel.h"
 #include "seedchain_kernel.h"
 #include "window_kernel.h"
+#include "chain_fill.h"
 #include "host/wm_chain.h"
 
 
@@ -164,43 +165,6 @@ __global__ __launch_bounds__(64) void seed_merge_kernel(const uint32_t *__restri
 		t |= i > b && k[i - 1] == o.x;
 	}
 	if (__any(t) && threadIdx.x == 0) tie[j] = 1;
-}
-
-// chain DP fill: one wave per anchor set, LDS window of W anchors (28 B each: x, y, f, p, t); f and p go to fpvt
-__global__ __launch_bounds__(64) void chain_kernel(const wm_chain_job_t *jobs, const int *order, const wm128_t *anchors, int *fpvt, int W)
-{
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const int j = order[blockIdx.x];
-	const wm_chain_job_t jb = jobs[j];
-	uint64_t *sx = (uint64_t*)smem, *sy = sx + W;
-	int *sf = (int*)(sy + W), *sp = sf + W, *st = sp + W;
-	int *gf = fpvt + jb.a_off * 4, *gp = gf + jb.n, *gt = gp + 2 * (size_t)jb.n;      // slab per job: f | p | v (host) | t
-	wmk::chain_wave(jb, anchors, W, sx, sy, sf, sp, st, gf, gp, gt);
-}
-
-// large anchor sets: NWV waves cooperate on one job (chain_block); LDS = 28 B * W window + publish area
-template <int NWV>
-__global__ __launch_bounds__(64 * NWV) void chain_kernel_block(const wm_chain_job_t *jobs, const int *order, const wm128_t *anchors, int *fpvt, int W)
-{
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const int j = order[blockIdx.x];
-	const wm_chain_job_t jb = jobs[j];
-	uint64_t *sx = (uint64_t*)smem, *sy = sx + W;
-	int *sf = (int*)(sy + W), *sp = sf + W, *st = sp + W, *pub = st + W;
-	int *gf = fpvt + jb.a_off * 4, *gp = gf + jb.n, *gt = gp + 2 * (size_t)jb.n;
-	wmk::chain_block(jb, anchors, NWV, W, sx, sy, sf, sp, st, pub, gf, gp, gt);
-}
-// ... with the whole predecessor window of an anchor per step (chain_block_wide, round 6): blockDim / 64 wavefronts x KT tiles
-template <int KT>
-__global__ __launch_bounds__(1024) void chain_kernel_wide(const wm_chain_job_t *jobs, const int *order, const wm128_t *anchors, int *fpvt, int W, int kt_first)
-{
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	const int j = order[blockIdx.x];
-	const wm_chain_job_t jb = jobs[j];
-	uint64_t *sx = (uint64_t*)smem, *sy = sx + W;
-	int *sf = (int*)(sy + W), *sp = sf + W, *st = sp + W, *pub = st + W;
-	int *gf = fpvt + jb.a_off * 4, *gp = gf + jb.n, *gt = gp + 2 * (size_t)jb.n;
-	wmk::chain_block_wide<KT>(jb, anchors, (int)(blockDim.x >> 6), kt_first, W, sx, sy, sf, sp, st, pub, gf, gp, gt);
 }
 
 extern "C" float wm_last_aux_ms(const wm_ctx_t *c) { return c ? c->aux_ms : 0.f; }
@@ -1025,16 +989,14 @@ try {
 		hipLaunchKernelGGL(seed_kernel, dim3((int)jb.size()), dim3(64), 0, c->stream, ix, d_jobs, d_mini, d_out, d_occ, d_occ_off, d_res, d_first);
 		int herr = 0;
 		if (heap) {
-			constexpr int NWV = 8, kSmall = 256, kLarge = 4096;      // the window op's classes (wm_window.hip)
 			const int nj = (int)jb.size();
 			HIPCHK(hipMemsetAsync(d_herr, 0, 4, c->stream));
-			HIPCHK(hipFuncSetAttribute((const void*)seed_heap_kernel<NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-			hipLaunchKernelGGL(seed_heap_kernel<1>, dim3(nj), dim3(64), (size_t)WIN_HEAP_INTS(1) * 4 + (size_t)kSmall * 32, c->stream, ix, d_jobs, d_mini, d_out, d_hb0, d_hb1, d_occ, d_first,
-			                   d_occ_off, d_res, d_heap, -1, kSmall, kSmall, d_herr);
-			hipLaunchKernelGGL(seed_heap_kernel<NWV>, dim3(nj), dim3(64 * NWV), (size_t)WIN_HEAP_INTS(NWV) * 4 + (size_t)kLarge * 32, c->stream, ix, d_jobs, d_mini, d_out, d_hb0, d_hb1, d_occ, d_first,
-			                   d_occ_off, d_res, d_heap, kSmall, kLarge, kLarge, d_herr);
-			hipLaunchKernelGGL(seed_heap_kernel<NWV>, dim3(nj), dim3(64 * NWV), (size_t)WIN_HEAP_INTS(NWV) * 4, c->stream, ix, d_jobs, d_mini, d_out, d_hb0, d_hb1, d_occ, d_first,
-			                   d_occ_off, d_res, d_heap, kLarge, 0x7fffffff, 0, d_herr);
+			if (const int rc = wmk::heap_order_launch([&](auto nwv, size_t lds, int lo, int hi, int lds_cap) -> int {
+				constexpr int N = decltype(nwv)::value;
+				HIPCHK(hipFuncSetAttribute((const void*)seed_heap_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+				hipLaunchKernelGGL(seed_heap_kernel<N>, dim3(nj), dim3(64 * N), lds, c->stream, ix, d_jobs, d_mini, d_out, d_hb0, d_hb1, d_occ, d_first, d_occ_off, d_res, d_heap, lo, hi, lds_cap, d_herr);
+				return WM_OK;
+			})) return rc;
 		}
 		HIPCHK(hipEventRecord(c->ev[1], c->stream));
 		UBuf<wm_seed_res_t> res(jb.size() + 1, c);
@@ -1154,8 +1116,7 @@ try {
 	WM_SITE("chain.jobs+avg_qspan");
 	wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) {
 		jb[i].a_off = a_off[i]; jb[i].n = n_a[i];
-		jb[i].max_dist_x = par[i].max_dist_x; jb[i].min_dist_x = par[i].min_dist_x; jb[i].max_dist_y = par[i].max_dist_y; jb[i].bw = par[i].bw;
-		jb[i].max_skip = par[i].max_skip; jb[i].max_iter = par[i].max_iter; jb[i].gap_scale = par[i].gap_scale; jb[i].is_cdna = par[i].is_cdna != 0;
+		chain_par_to_job(par[i], jb[i]);
 		jb[i].avg_qspan = n_a[i] > 0 ? wm::chain_avg_qspan(n_a[i], a + a_off[i]) : 0.f;
 		order[i] = (int)i;
 	});
@@ -1189,31 +1150,19 @@ try {
 	HIPCHK(hipMemcpyAsync(d_a, a, tot * sizeof(wm128_t), hipMemcpyHostToDevice, c->stream));
 	const double tt1 = trace ? now_ms() : 0;
 	HIPCHK(hipEventRecord(c->ev[0], c->stream));
-	{   // classes (order is grouped by class, largest jobs first inside a class): LDS footprint = 28 B * W
-		HIPCHK(hipFuncSetAttribute((const void*)chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		constexpr int NWV = 8;
-		HIPCHK(hipFuncSetAttribute((const void*)chain_kernel_block<NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		int b = 0;
-		for (int k = 0; k < 4; ++k) {                        // 0 dense (8 waves, W 4096) | 1 large sparse (1 wave, W 1024) | 2 n <= 1024 | 3 n <= 256
+	{   // the four class lists are stretches of `order` (grouped by class, largest jobs first inside a class); the dense fill: WM_CHAIN_WIDE is read once per process, the
+		// geometry and kt_first on every call (chain_fill.h)
+		static const bool wide = chain_dense_env(false).wide;
+		ChainDense dense = chain_dense_env(true);
+		dense.wide = wide;
+		ChainFillList cls[4];
+		for (int k = 0, b = 0; k < 4; ++k) {
 			int e = b;
 			while (e < n && klass_of(order[e]) == k) ++e;
-			if (e > b) {
-				// WM_CHAIN_WIDE=0: the round-5 dense fill; WM_CHAIN_WIDE_GEOM=<wavefronts>x<tiles per wavefront> (16x5 | 8x10 | 16x3 | 8x5 | 4x10; tools/chain_fill_probe.py)
-				static const bool wide = !(getenv("WM_CHAIN_WIDE") && atoi(getenv("WM_CHAIN_WIDE")) == 0);
-				int gw = 16, gk = 5;
-				if (const char *g = getenv("WM_CHAIN_WIDE_GEOM")) sscanf(g, "%dx%d", &gw, &gk);
-				if ((gk != 10 && gk != 3 && gk != 5) || gw < 1 || gw > 16 || gw * gk > 128) { gw = 16; gk = 5; }      // (the instantiated tile counts; chain_block_wide: NT <= 128)
-				const int kt_first = getenv("WM_CHAIN_WIDE_FIRST") ? std::min(gk, std::max(1, atoi(getenv("WM_CHAIN_WIDE_FIRST")))) : gk;      // tiles per wavefront in an anchor's first step (seedchain_kernel.h)
-				if (k == 0 && wide) {
-					const size_t lds = (size_t)4096 * 28 + (size_t)gw * gk * 69 * 4 + 64;
-					if (gk == 10) { HIPCHK(hipFuncSetAttribute((const void*)chain_kernel_wide<10>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); hipLaunchKernelGGL(chain_kernel_wide<10>, dim3(e - b), dim3(64 * gw), lds, c->stream, d_jobs, d_order + b, d_a, d_fpvt, 4096, kt_first); }
-					else if (gk == 3) { HIPCHK(hipFuncSetAttribute((const void*)chain_kernel_wide<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); hipLaunchKernelGGL(chain_kernel_wide<3>, dim3(e - b), dim3(64 * gw), lds, c->stream, d_jobs, d_order + b, d_a, d_fpvt, 4096, kt_first); }
-					else { HIPCHK(hipFuncSetAttribute((const void*)chain_kernel_wide<5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); hipLaunchKernelGGL(chain_kernel_wide<5>, dim3(e - b), dim3(64 * gw), lds, c->stream, d_jobs, d_order + b, d_a, d_fpvt, 4096, kt_first); }
-				} else if (k == 0) hipLaunchKernelGGL(chain_kernel_block<NWV>, dim3(e - b), dim3(64 * NWV), (size_t)4096 * 28 + NWV * 69 * 4 + 64, c->stream, d_jobs, d_order + b, d_a, d_fpvt, 4096);
-				else hipLaunchKernelGGL(chain_kernel, dim3(e - b), dim3(64), (size_t)(k == 3 ? 256 : 1024) * 28, c->stream, d_jobs, d_order + b, d_a, d_fpvt, k == 3 ? 256 : 1024);
-			}
+			cls[k] = { d_order + b, 0, e - b };
 			b = e;
 		}
+		if (const int rc = chain_fill_launch(c->stream, d_jobs, d_a, d_fpvt, cls, dense)) return rc;
 	}
 	HIPCHK(hipEventRecord(c->ev[1], c->stream));
 	const double tt2 = trace ? now_ms() : 0;

@@ -31,6 +31,14 @@ extern "C" void wm_exts2_stats(uint64_t *out2, int reset)
 // ======================================================================================================
 // GpuOps: the product implementation of the mapper's device operations
 // ======================================================================================================
+// the name keys of a request list (self / all-vs-all mapping): all requests of a call come from one mapper, so all or none carry one; empty = none
+template <class R> static std::vector<wm_qkey_t> name_keys(const std::vector<R*> &reqs)
+{
+	std::vector<wm_qkey_t> keys;
+	if (reqs[0]->has_key) { keys.resize(reqs.size()); for (size_t i = 0; i < reqs.size(); ++i) keys[i] = { reqs[i]->q_lo, reqs[i]->q_eq }; }
+	return keys;
+}
+
 // one device context (stream + arena + staging slab) worth of batched operations; GpuOps below hands the contexts out
 struct GpuOpsCtx {
 	wm_ctx_t *c;
@@ -81,8 +89,7 @@ struct GpuOpsCtx {
 		std::vector<int32_t> nm(n), ql(n), na(n), rl(n);
 		size_t tot = 0;
 		for (int i = 0; i < n; ++i) { moff[i] = tot; nm[i] = reqs[i]->n_mini; ql[i] = reqs[i]->qlen; tot += reqs[i]->n_mini; }
-		std::vector<wm_qkey_t> keys;                  // name keys (self / all-vs-all mapping): all requests of a call come from one mapper, so all or none carry one
-		if (reqs[0]->has_key) { keys.resize(n); for (int i = 0; i < n; ++i) keys[i] = { reqs[i]->q_lo, reqs[i]->q_eq }; }
+		const std::vector<wm_qkey_t> keys = name_keys(reqs);
 		UBuf<wm128_t> mini(tot + 1, c);
 		WM_SITE("seed.pack");
 		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) { memcpy(mini.data() + moff[i], reqs[i]->mini, (size_t)reqs[i]->n_mini * sizeof(wm128_t)); });
@@ -109,8 +116,7 @@ struct GpuOpsCtx {
 		size_t tot = 0;
 		for (int i = 0; i < n; ++i) {
 			aoff[i] = tot; na[i] = (int)reqs[i]->a.size(); tot += reqs[i]->a.size();
-			wm::ChainReq &r = *reqs[i];
-			par[i] = { r.max_dist_x, r.min_dist_x, r.max_dist_y, r.bw, r.max_skip, r.max_iter, r.min_cnt, r.min_sc, r.gap_scale, r.is_cdna ? 1 : 0 };
+			par[i] = chain_par_of(*reqs[i]);
 		}
 		UBuf<wm128_t> a(tot + 1, c);
 		UBuf<uint64_t> u(tot + 1, c);
@@ -141,8 +147,7 @@ struct GpuOpsCtx {
 			}
 		const double ts = now_ms();
 		UBuf<wm_window_job_t> jobs(n, c);
-		std::vector<wm_qkey_t> keys;              // name keys (self / all-vs-all mapping): all requests of a call come from one mapper, so all or none carry one
-		if (reqs[0]->has_key) { keys.resize(n); for (int i = 0; i < n; ++i) keys[i] = { reqs[i]->q_lo, reqs[i]->q_eq }; }
+		const std::vector<wm_qkey_t> keys = name_keys(reqs);
 		size_t stage = 0, npre = 0;
 		for (int i = 0; i < n; ++i) {
 			const wm::WindowReq &r = *reqs[i];
@@ -152,7 +157,7 @@ struct GpuOpsCtx {
 			if (r.len <= 0) j.seq_off = -2;
 			else if (resident && r.dev_off >= 0) j.seq_off = r.dev_off;
 			else { j.seq_off = -1; j.stage_off = stage; stage += (size_t)r.len; }
-			j.par = { r.max_dist_x, r.min_dist_x, r.max_dist_y, r.bw, r.max_skip, r.max_iter, r.min_cnt, r.min_sc, r.gap_scale, r.is_cdna ? 1 : 0 };
+			j.par = chain_par_of(r);
 		}
 		UBuf<uint8_t> seqs(stage + 1, c);
 		UBuf<wm128_t> pre(npre + 1, c);
@@ -164,31 +169,25 @@ struct GpuOpsCtx {
 			if (!r.pre.empty()) memcpy(pre.data() + jobs[i].pre_off, r.pre.data(), r.pre.size() * sizeof(wm128_t));
 		});
 		if (hipSetDevice(c->device) != hipSuccess) { error = "hipSetDevice failed"; return; }
-		c->aux_ms = 0;
-		for (int round = 0; round < 2; ++round) {
-			ArenaMark mark(c);
-			WinDev D;
-			int rc = window_launch(c, n, jobs.data(), seqs.data(), stage, pre.data(), npre, reqs[0]->max_occ, reqs[0]->flag, round == 1, D, keys.empty() ? 0 : keys.data(), reqs[0]->sdust_thres);
-			if (!rc) rc = window_verdict(D, round);
-			if (rc < 0) { fail("window"); return; }
-			if (rc == 1) continue;
-			UBuf<uint64_t> up((size_t)D.tot[0] + 1, c);
-			UBuf<wm128_t> ap((size_t)D.tot[1] + 1, c);
-			if (window_fetch(c, D, n, res.data(), up.data(), ap.data())) { fail("window"); return; }
-			t_sketch += now_ms() - ts;
-			aux_us += c->aux_ms * 1e3;
-			WM_SITE("window.unpack");
-			wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) {
-				wm::WindowReq &r = *reqs[i];
-				const wm_window_res_t &o = res[i];
-				r.rep_len = o.rep_len; r.n_anchors = o.n_anchors;
-				r.u.assign(up.begin() + o.u_off, up.begin() + o.u_off + o.n_u);
-				r.a.resize((size_t)o.n_v);
-				if (o.n_v) memcpy(r.a.data(), ap.data() + o.a_off, (size_t)o.n_v * sizeof(wm128_t));
-			});
-			return;
-		}
-		error = "window retry did not converge";
+		std::optional<UBuf<uint64_t>> up;           // the result pools: sized once the call knows its totals, in the pinned slab
+		std::optional<UBuf<wm128_t>> ap;
+		if (window_run(c, n, jobs.data(), keys.empty() ? 0 : keys.data(), seqs.data(), stage, pre.data(), npre, reqs[0]->max_occ, reqs[0]->flag, reqs[0]->sdust_thres, res.data(),
+		               [&](uint32_t n_chains, uint32_t n_anchors, uint64_t **u_pool, wm128_t **a_pool) {
+			up.emplace((size_t)n_chains + 1, c); ap.emplace((size_t)n_anchors + 1, c);
+			*u_pool = up->data(); *a_pool = ap->data();
+			return WM_OK;
+		})) { fail("window"); return; }
+		t_sketch += now_ms() - ts;
+		aux_us += c->aux_ms * 1e3;
+		WM_SITE("window.unpack");
+		wm::parallel_for(c->host_threads, (size_t)n, [&](size_t i) {
+			wm::WindowReq &r = *reqs[i];
+			const wm_window_res_t &o = res[i];
+			r.rep_len = o.rep_len; r.n_anchors = o.n_anchors;
+			r.u.assign(up->begin() + o.u_off, up->begin() + o.u_off + o.n_u);
+			r.a.resize((size_t)o.n_v);
+			if (o.n_v) memcpy(r.a.data(), ap->data() + o.a_off, (size_t)o.n_v * sizeof(wm128_t));
+		});
 	}
 	void ksw_batch(const wm_ksw_score_t &sc, std::vector<wm::KswReq*> &reqs)
 	{

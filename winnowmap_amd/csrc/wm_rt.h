@@ -28,6 +28,7 @@
 #include <chrono>
 #include <atomic>
 #include <mutex>
+#include <functional>
 #include <unistd.h>
 #include "host/wm_core.h"
 #include "host/wm_index.h"
@@ -153,8 +154,20 @@ int sketch_launch(wm_ctx_t *c, int n, const wm_sketch_job_t *h_jobs, const wm_sk
                   double *d_so, uint64_t *d_sx, uint32_t *d_sy, uint32_t *d_sl, wm128_t *d_out, int *d_cnt, bool allow_long, uint8_t *mem = 0, size_t mem_bytes = 0);
 
 // wm_window.hip
-struct WinDev { wm_win_res_t *d_res; uint64_t *d_upool; wm128_t *d_vpool; uint64_t *d_ctr; uint64_t ctr[4]; uint32_t tot[3]; };
-int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
-                  int max_occ, int64_t flag, bool slot_full, WinDev &D, const wm_qkey_t *keys = 0, int sdust_thres = 0);
-int window_fetch(wm_ctx_t *c, const WinDev &D, int n, wm_window_res_t *res, uint64_t *u_pool, wm128_t *a_pool);
-int window_verdict(const WinDev &D, int round);
+// One window call: launch, verdict, a second launch with full-size minimizer slots if the first asks for one, fetch. Once the totals are known `sized` is called with
+// them and hands back the two result pools the fetch fills (or an error, which ends the call); it runs at most once.
+typedef std::function<int(uint32_t n_chains, uint32_t n_anchors, uint64_t **u_pool, wm128_t **a_pool)> WinSized;
+int window_run(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const wm_qkey_t *keys, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
+               int max_occ, int64_t flag, int sdust_thres, wm_window_res_t *res, const WinSized &sized);
+
+// mm_chain_dp's parameters between their three carriers. A request (wm::ChainReq, wm::WindowReq) -> the C ABI's struct ...
+template <class R> inline wm_chain_par_t chain_par_of(const R &r)
+{
+	return { r.max_dist_x, r.min_dist_x, r.max_dist_y, r.bw, r.max_skip, r.max_iter, r.min_cnt, r.min_sc, r.gap_scale, r.is_cdna ? 1 : 0 };
+}
+// ... and that struct -> a device job (wm_chain_job_t, wm_win_job_t): the eight the fill reads; min_cnt / min_sc belong to the extraction and only wm_win_job_t has them
+template <class J> inline void chain_par_to_job(const wm_chain_par_t &p, J &j)
+{
+	j.max_dist_x = p.max_dist_x; j.min_dist_x = p.min_dist_x; j.max_dist_y = p.max_dist_y; j.bw = p.bw;
+	j.max_skip = p.max_skip; j.max_iter = p.max_iter; j.gap_scale = p.gap_scale; j.is_cdna = p.is_cdna != 0;
+}

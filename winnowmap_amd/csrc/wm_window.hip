@@ -6,6 +6,7 @@
 #include "sketch_kernel.h"
 #include "seedchain_kernel.h"
 #include "window_kernel.h"
+#include "chain_fill.h"
 #include "sdust_kernel.h"
 #include "host/wm_core.h"
 #include "host/wm_sdust.h"
@@ -286,45 +287,6 @@ __global__ __launch_bounds__(64) void win_plan_list_kernel(const wm_win_job_t *_
 	wmk::win_plan_wave(jobs[j], j, r.a_off, r.n_a, anchors + r.a_off, cj, lists, counts, n_jobs);
 }
 
-// the fills of seedchain_kernel.h over a device-side job list (block b serves list[b]; blocks beyond *count leave)
-__global__ __launch_bounds__(64) void win_chain_kernel(const wm_chain_job_t *jobs, const int *list, const int *count, const wm128_t *anchors, int *fpvt, int W)
-{
-	WM_SETPRIO(2);
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	if ((int)blockIdx.x >= *count) return;
-	const wm_chain_job_t jb = jobs[list[blockIdx.x]];
-	uint64_t *sx = (uint64_t*)smem, *sy = sx + W;
-	int *sf = (int*)(sy + W), *sp = sf + W, *st = sp + W;
-	int *gf = fpvt + jb.a_off * 4, *gp = gf + jb.n, *gt = gp + 2 * (size_t)jb.n;
-	wmk::chain_wave(jb, anchors, W, sx, sy, sf, sp, st, gf, gp, gt);
-}
-template <int NWV>
-__global__ __launch_bounds__(64 * NWV) void win_chain_kernel_block(const wm_chain_job_t *jobs, const int *list, const int *count, const wm128_t *anchors, int *fpvt, int W)
-{
-	WM_SETPRIO(2);
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	if ((int)blockIdx.x >= *count) return;
-	const wm_chain_job_t jb = jobs[list[blockIdx.x]];
-	uint64_t *sx = (uint64_t*)smem, *sy = sx + W;
-	int *sf = (int*)(sy + W), *sp = sf + W, *st = sp + W, *pub = st + W;
-	int *gf = fpvt + jb.a_off * 4, *gp = gf + jb.n, *gt = gp + 2 * (size_t)jb.n;
-	wmk::chain_block(jb, anchors, NWV, W, sx, sy, sf, sp, st, pub, gf, gp, gt);
-}
-
-// the dense fill with the whole predecessor window of an anchor per step (seedchain_kernel.h: chain_block_wide): 16 wavefronts x KT tiles
-template <int KT>
-__global__ __launch_bounds__(1024) void win_chain_kernel_wide(const wm_chain_job_t *jobs, const int *list, const int *count, const wm128_t *anchors, int *fpvt, int W, int kt_first)
-{
-	WM_SETPRIO(2);
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	if ((int)blockIdx.x >= *count) return;
-	const wm_chain_job_t jb = jobs[list[blockIdx.x]];
-	uint64_t *sx = (uint64_t*)smem, *sy = sx + W;
-	int *sf = (int*)(sy + W), *sp = sf + W, *st = sp + W, *pub = st + W;
-	int *gf = fpvt + jb.a_off * 4, *gp = gf + jb.n, *gt = gp + 2 * (size_t)jb.n;
-	wmk::chain_block_wide<KT>(jb, anchors, 16, kt_first, W, sx, sy, sf, sp, st, pub, gf, gp, gt);
-}
-
 // src/chain.c:89-165 per job; f, p staged in LDS when the job fits (lo, lds_cap], global slab otherwise (lds_cap = 0)
 __global__ __launch_bounds__(64) void win_extract_kernel(const wm_win_job_t *__restrict__ jobs, wm_win_res_t *res, wm128_t *anchors, int *fpvt, uint64_t *zu, wm128_t *bbuf, wm128_t *wbuf,
                                                           int lo, int lds_cap, uint64_t *u_pool, wm128_t *v_pool, uint64_t *pool_ctr)
@@ -347,12 +309,12 @@ __global__ __launch_bounds__(64) void win_extract_kernel(const wm_win_job_t *__r
 		wmk::win_extract_wave<true>(n, jb.min_cnt, jb.min_sc, anchors + r.a_off, gf, gp, gv, gt, zu + r.a_off, bbuf + r.a_off, wbuf + r.a_off, ws, res + j, u_pool, v_pool, pool_ctr);
 }
 
+// what a launched call leaves for its verdict and fetch: the result table and the dense pools on the device, the counters (ctr; tot = chains, anchors, worst err)
+struct WinDev { wm_win_res_t *d_res; uint64_t *d_upool; wm128_t *d_vpool; uint64_t *d_ctr; uint64_t ctr[4]; uint32_t tot[3]; };
 // device side of one call: everything up to the dense result pools; the caller copies them out. slot_full: full-size minimizer slots (retry)
-int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
+static int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
                          int max_occ, int64_t flag, bool slot_full, WinDev &D, const wm_qkey_t *keys, int sdust_thres)
 {
-	const int w = c->skp.w;
-	(void)w;
 	// host tables
 	UBuf<wm_win_job_t> jb(n, c);
 	UBuf<wm_sketch_job_t> sj(n, c);
@@ -369,8 +331,8 @@ int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t
 		d.seq_off = has_seq ? 0 : -1; d.pre_off = s.pre_off; d.len = s.len; d.n_pre = s.n_pre; d.max_occ = max_occ;
 		// (the name bits travel only with a key: skip_seed with qname == NULL ignores them, src/map.c:135)
 		d.seed_flag = (int32_t)(flag & (0x100000 | 0x200000 | 0x400000 | (keys && c->d_name_rank ? 3 : 0))); d.q_lo = keys ? keys[i].lo : 0; d.q_eq = keys ? (int32_t)keys[i].eq : 0;
-		d.max_dist_x = s.par.max_dist_x; d.min_dist_x = s.par.min_dist_x; d.max_dist_y = s.par.max_dist_y; d.bw = s.par.bw; d.max_skip = s.par.max_skip; d.max_iter = s.par.max_iter;
-		d.min_cnt = s.par.min_cnt; d.min_sc = s.par.min_sc; d.gap_scale = s.par.gap_scale; d.is_cdna = s.par.is_cdna != 0;
+		chain_par_to_job(s.par, d);
+		d.min_cnt = s.par.min_cnt; d.min_sc = s.par.min_sc;
 		wm_sketch_job_t &k = sj[i];
 		k.len = has_seq ? s.len : 0;
 		k.cap = has_seq ? (slot_full ? s.len + 1 : s.len / 8 + 16) : 0;
@@ -444,17 +406,15 @@ int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t
 	wm_index_view_t ix = { c->d_hkey, c->d_hval, c->d_P, c->hbits, 0, c->d_name_rank, c->d_seq_len };
 	hipLaunchKernelGGL(win_seed_kernel, dim3(n), dim3(64), 0, c->stream, ix, d_jobs, d_sj, d_mcnt, d_mini, d_pre, d_occ, d_first, d_emit, d_a, d_ctr, cap, D.d_res, (int*)(d_ctr + 3));
 	const size_t ws_bytes = (size_t)wmk::WIN_WS_PAD * 4;
-	static const int kSmall = wmk::WIN_SMALL, kLarge = 4096;
-	if (heap) {      // three size classes of the seeded part, LDS sized per class: the bulk by one wavefront, up to kLarge by a workgroup in LDS, beyond it in global memory
-		constexpr int NWV = 8;
+	constexpr int kSmall = wmk::WIN_SMALL, kLarge = wmk::WIN_LARGE;
+	if (heap) {      // three size classes of the seeded part, LDS sized per class (window_kernel.h: heap_order_launch)
 		int *d_herr = (int*)(d_ctr + 3) + 1;
-		HIPCHK(hipFuncSetAttribute((const void*)win_heap_kernel<NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		hipLaunchKernelGGL(win_heap_kernel<1>, dim3(n), dim3(64), (size_t)WIN_HEAP_INTS(1) * 4 + (size_t)kSmall * 32, c->stream, ix, d_jobs, d_sj, d_mini, d_occ, d_first, d_a, d_b, d_w, D.d_res,
-		                   d_heap, -1, kSmall, kSmall, d_herr);
-		hipLaunchKernelGGL(win_heap_kernel<NWV>, dim3(n), dim3(64 * NWV), (size_t)WIN_HEAP_INTS(NWV) * 4 + (size_t)kLarge * 32, c->stream, ix, d_jobs, d_sj, d_mini, d_occ, d_first, d_a, d_b, d_w, D.d_res,
-		                   d_heap, kSmall, kLarge, kLarge, d_herr);
-		hipLaunchKernelGGL(win_heap_kernel<NWV>, dim3(n), dim3(64 * NWV), (size_t)WIN_HEAP_INTS(NWV) * 4, c->stream, ix, d_jobs, d_sj, d_mini, d_occ, d_first, d_a, d_b, d_w, D.d_res,
-		                   d_heap, kLarge, 0x7fffffff, 0, d_herr);
+		if (const int rc = wmk::heap_order_launch([&](auto nwv, size_t lds, int lo, int hi, int lds_cap) -> int {
+			constexpr int N = decltype(nwv)::value;
+			HIPCHK(hipFuncSetAttribute((const void*)win_heap_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+			hipLaunchKernelGGL(win_heap_kernel<N>, dim3(n), dim3(64 * N), lds, c->stream, ix, d_jobs, d_sj, d_mini, d_occ, d_first, d_a, d_b, d_w, D.d_res, d_heap, lo, hi, lds_cap, d_herr);
+			return WM_OK;
+		})) return rc;
 	}
 	// the bulk (jobs of at most WIN_SMALL anchors: one MCAS window yields ~100) finishes in one kernel; the rest goes class by class
 	HIPCHK(hipFuncSetAttribute((const void*)win_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -503,22 +463,11 @@ int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t
 			HIPCHK(ctx_sync(c));                 // (the staging buffers above are released at the end of this block)
 		}
 	}
-	{   // the fill, per class list: 0 dense (8 waves, W 4096) | 1 large sparse (1 wave, W 1024) | 2 n <= 1024 | 3 n <= 256
-		HIPCHK(hipFuncSetAttribute((const void*)win_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		constexpr int NWV = 8;
-		// WM_CHAIN_WIDE=0: the round-5 dense fill (8 wavefronts, 512 predecessors per step); default: 16 wavefronts x 5 tiles = a whole max_iter window per step
-		static const bool wide = !(getenv("WM_CHAIN_WIDE") && atoi(getenv("WM_CHAIN_WIDE")) == 0);
-		if (wide) {
-			HIPCHK(hipFuncSetAttribute((const void*)win_chain_kernel_wide<5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-			static const int kt_first = getenv("WM_CHAIN_WIDE_FIRST") ? std::min(5, std::max(1, atoi(getenv("WM_CHAIN_WIDE_FIRST")))) : 5;      // tiles per wavefront in an anchor's first step (seedchain_kernel.h)
-			hipLaunchKernelGGL(win_chain_kernel_wide<5>, dim3(n), dim3(1024), (size_t)4096 * 28 + 80 * 69 * 4 + 64, c->stream, d_cj, d_lists, d_counts, d_a, d_fpvt, 4096, kt_first);
-		} else {
-			HIPCHK(hipFuncSetAttribute((const void*)win_chain_kernel_block<NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-			hipLaunchKernelGGL(win_chain_kernel_block<NWV>, dim3(n), dim3(64 * NWV), (size_t)4096 * 28 + NWV * 69 * 4 + 64, c->stream, d_cj, d_lists, d_counts, d_a, d_fpvt, 4096);
-		}
-		hipLaunchKernelGGL(win_chain_kernel, dim3(n), dim3(64), (size_t)1024 * 28, c->stream, d_cj, d_lists + n, d_counts + 1, d_a, d_fpvt, 1024);
-		hipLaunchKernelGGL(win_chain_kernel, dim3(n), dim3(64), (size_t)1024 * 28, c->stream, d_cj, d_lists + 2 * (size_t)n, d_counts + 2, d_a, d_fpvt, 1024);
-		// (class 3, at most 256 anchors: served by win_small_kernel)
+	{   // the fill, per class list (chain_fill.h). The dense fill is 16 x 5 — a whole max_iter window per step — or, with WM_CHAIN_WIDE=0, the round-5 one; the
+		// switches are read once per process. Class 3, at most WIN_SMALL anchors, was served by win_small_kernel
+		static const ChainDense dense = chain_dense_env(false);
+		const ChainFillList cls[4] = { { d_lists, d_counts, n }, { d_lists + n, d_counts + 1, n }, { d_lists + 2 * (size_t)n, d_counts + 2, n }, { 0, 0, 0 } };
+		if (const int rc = chain_fill_launch(c->stream, d_cj, d_a, d_fpvt, cls, dense)) return rc;
 	}
 	HIPCHK(hipFuncSetAttribute((const void*)win_extract_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 	hipLaunchKernelGGL(win_extract_kernel, dim3(n), dim3(64), ws_bytes + (size_t)kLarge * 16, c->stream, d_jobs, D.d_res, d_a, d_fpvt, d_zu, d_b, d_w, kSmall, kLarge, D.d_upool, D.d_vpool, d_ctr + 1);
@@ -535,7 +484,7 @@ int window_launch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t
 }
 
 // copies the result table and the two dense pools of a launched call to the host (pools sized by the caller from D.tot)
-int window_fetch(wm_ctx_t *c, const WinDev &D, int n, wm_window_res_t *res, uint64_t *u_pool, wm128_t *a_pool)
+static int window_fetch(wm_ctx_t *c, const WinDev &D, int n, wm_window_res_t *res, uint64_t *u_pool, wm128_t *a_pool)
 {
 	UBuf<wm_win_res_t> hr(n, c);
 	HIPCHK(hipMemcpyAsync(hr.data(), D.d_res, (size_t)n * sizeof(wm_win_res_t), hipMemcpyDeviceToHost, c->stream));
@@ -549,12 +498,33 @@ int window_fetch(wm_ctx_t *c, const WinDev &D, int n, wm_window_res_t *res, uint
 	return WM_OK;
 }
 // verdict of a launched call: 0 = fetch, 1 = launch again with full-size minimizer slots, < 0 = error
-int window_verdict(const WinDev &D, int round)
+static int window_verdict(const WinDev &D, int round)
 {
 	if (D.tot[2] == 2) return set_err(WM_ENOMEM, "window batch does not fit the arena (anchor pool)");
 	if (D.ctr[3] >> 32) return set_err(WM_EINTERNAL, "heap-ordered seeding: a job's occurrence counts contradict its anchor count");
 	if (D.tot[2] == 1) return round == 0 ? 1 : set_err(WM_EINTERNAL, "minimizer slot overflow at full size");
 	return 0;
+}
+
+// one window call, shared by wm_window_batch* and the mapper (wm_rt.h): two rounds at most, the second with full-size minimizer slots
+int window_run(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const wm_qkey_t *keys, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
+               int max_occ, int64_t flag, int sdust_thres, wm_window_res_t *res, const WinSized &sized)
+{
+	c->aux_ms = 0;
+	for (int round = 0; round < 2; ++round) {
+		ArenaMark mark(c);
+		WinDev D;
+		int rc = window_launch(c, n, jobs, seqs, seqs_bytes, pre, n_pre_total, max_occ, flag, round == 1, D, keys, sdust_thres);
+		if (rc) return rc;
+		rc = window_verdict(D, round);
+		if (rc < 0) return rc;
+		if (rc == 1) continue;
+		uint64_t *u_pool = 0;
+		wm128_t *a_pool = 0;
+		if ((rc = sized(D.tot[0], D.tot[1], &u_pool, &a_pool)) != 0) return rc;
+		return window_fetch(c, D, n, res, u_pool, a_pool);
+	}
+	return set_err(WM_EINTERNAL, "window retry did not converge");
 }
 
 extern "C" int wm_window_batch(wm_ctx_t *c, int n, const wm_window_job_t *jobs, const uint8_t *seqs, size_t seqs_bytes, const wm128_t *pre, size_t n_pre_total,
@@ -578,22 +548,14 @@ try {
 	if (n <= 0) return WM_OK;
 	if (!jobs || !res) return set_err(WM_EINVAL, "null argument");
 	HIPCHK(hipSetDevice(c->device));
-	c->aux_ms = 0;
-	for (int round = 0; round < 2; ++round) {
-		ArenaMark mark(c);
-		WinDev D;
-		int rc = window_launch(c, n, jobs, seqs, seqs_bytes, pre, n_pre_total, max_occ, flag, round == 1, D, keys, sdust_thres);
-		if (rc) return rc;
-		rc = window_verdict(D, round);
-		if (rc < 0) return rc;
-		if (rc == 1) continue;
-		if (u_used) *u_used = D.tot[0];
-		if (a_used) *a_used = D.tot[1];
-		if (D.tot[0] > u_cap || D.tot[1] > a_cap) return set_err(WM_ENOMEM, "result pools too small: need %u chains and %u anchors", D.tot[0], D.tot[1]);
-		if ((D.tot[0] && !u_pool) || (D.tot[1] && !a_pool)) return set_err(WM_EINVAL, "null result pool");
-		return window_fetch(c, D, n, res, u_pool, a_pool);
-	}
-	return set_err(WM_EINTERNAL, "window retry did not converge");
+	return window_run(c, n, jobs, keys, seqs, seqs_bytes, pre, n_pre_total, max_occ, flag, sdust_thres, res, [&](uint32_t n_chains, uint32_t n_anchors, uint64_t **up, wm128_t **ap) {
+		if (u_used) *u_used = n_chains;
+		if (a_used) *a_used = n_anchors;
+		if (n_chains > u_cap || n_anchors > a_cap) return set_err(WM_ENOMEM, "result pools too small: need %u chains and %u anchors", n_chains, n_anchors);
+		if ((n_chains && !u_pool) || (n_anchors && !a_pool)) return set_err(WM_EINVAL, "null result pool");
+		*up = u_pool; *ap = a_pool;
+		return WM_OK;
+	});
 }
 catch (const std::bad_alloc &) { return set_err(WM_ENOMEM, "out of host memory"); }
 

@@ -275,12 +275,10 @@ class Context:
                                    max_occ, flag, out.ctypes.data, out_cap, out_off.ctypes.data, n_a.ctypes.data, rep_len.ctypes.data))
         return out, out_off, n_a, rep_len
 
-    def window_batch_keyed(self, jobs, keys, seqs, pre, max_occ, flag, u_cap, a_cap):
-        """wm_window_batch_keyed. jobs: structured array WINDOW_JOB; keys: uint32 [n, 2] or None (= wm_window_batch); seqs: uint8 staging codes; pre: uint64 [n_pre, 2].
-        Returns (res WINDOW_RES [n], u_pool, a_pool [.., 2])."""
-        L = lib()
-        L.wm_window_batch_keyed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int64,
-                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    def _window(self, fn, extra, jobs, keys, seqs, pre, max_occ, flag, u_cap, a_cap):
+        """the two window calls below: fn = the C symbol, extra = what it takes between `flag` and the results ((ctypes type, value) pairs)"""
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int64] + [t for t, _ in extra] + \
+                      [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         n = len(jobs)
         jobs = np.ascontiguousarray(jobs, WINDOW_JOB)
         keys = None if keys is None else np.ascontiguousarray(keys, np.uint32).reshape(n, 2)
@@ -289,27 +287,19 @@ class Context:
         res = np.zeros(n, WINDOW_RES)
         u_pool, a_pool = np.zeros(u_cap + 1, np.uint64), np.zeros((a_cap + 1, 2), np.uint64)
         uu, au = C.c_size_t(), C.c_size_t()
-        _chk(L.wm_window_batch_keyed(self._h, n, jobs.ctypes.data, None if keys is None else keys.ctypes.data, seqs.ctypes.data, seqs.nbytes, pre.ctypes.data, len(pre),
-                                     max_occ, flag, res.ctypes.data, u_pool.ctypes.data, u_cap, C.byref(uu), a_pool.ctypes.data, a_cap, C.byref(au)))
+        _chk(fn(self._h, n, jobs.ctypes.data, None if keys is None else keys.ctypes.data, seqs.ctypes.data, seqs.nbytes, pre.ctypes.data, len(pre),
+                max_occ, flag, *[v for _, v in extra], res.ctypes.data, u_pool.ctypes.data, u_cap, C.byref(uu), a_pool.ctypes.data, a_cap, C.byref(au)))
         return res, u_pool[:uu.value], a_pool[:au.value]
+
+    def window_batch_keyed(self, jobs, keys, seqs, pre, max_occ, flag, u_cap, a_cap):
+        """wm_window_batch_keyed. jobs: structured array WINDOW_JOB; keys: uint32 [n, 2] or None (= wm_window_batch); seqs: uint8 staging codes; pre: uint64 [n_pre, 2].
+        Returns (res WINDOW_RES [n], u_pool, a_pool [.., 2])."""
+        return self._window(lib().wm_window_batch_keyed, (), jobs, keys, seqs, pre, max_occ, flag, u_cap, a_cap)
 
     def window_batch_dust(self, jobs, keys, seqs, pre, max_occ, flag, sdust_thres, u_cap, a_cap):
         """wm_window_batch_dust: window_batch_keyed with the -T threshold — with sdust_thres > 0 every job's minimizers are squeezed by the SDUST intervals of
         its sequence before the seeding (mm_dust_minier, src/map.c:43-67); 0 = window_batch_keyed. Same arguments and results otherwise."""
-        L = lib()
-        L.wm_window_batch_dust.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int64, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        n = len(jobs)
-        jobs = np.ascontiguousarray(jobs, WINDOW_JOB)
-        keys = None if keys is None else np.ascontiguousarray(keys, np.uint32).reshape(n, 2)
-        seqs = np.ascontiguousarray(seqs, np.uint8)
-        pre = np.ascontiguousarray(pre, np.uint64).reshape(-1, 2)
-        res = np.zeros(n, WINDOW_RES)
-        u_pool, a_pool = np.zeros(u_cap + 1, np.uint64), np.zeros((a_cap + 1, 2), np.uint64)
-        uu, au = C.c_size_t(), C.c_size_t()
-        _chk(L.wm_window_batch_dust(self._h, n, jobs.ctypes.data, None if keys is None else keys.ctypes.data, seqs.ctypes.data, seqs.nbytes, pre.ctypes.data, len(pre),
-                                    max_occ, flag, sdust_thres, res.ctypes.data, u_pool.ctypes.data, u_cap, C.byref(uu), a_pool.ctypes.data, a_cap, C.byref(au)))
-        return res, u_pool[:uu.value], a_pool[:au.value]
+        return self._window(lib().wm_window_batch_dust, ((C.c_int, sdust_thres),), jobs, keys, seqs, pre, max_occ, flag, u_cap, a_cap)
 
     def sdust_batch(self, seqs, seq_off, lens, thres, resident=None):
         """wm_sdust_batch: the SDUST intervals (sdust_core with W = 64, src/sdust.c:134-164) of n sequences of 0..4 codes. seqs: uint8 staging codes; sequence i
