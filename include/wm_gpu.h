@@ -245,6 +245,37 @@ int wm_debug_stripe_timing(uint64_t *out16, int reset);
  * host/wm_align.cpp). m = 5, mat = 5x5. Runs on the HOST (the mapper needs it twice per inversion candidate / boundary exon only);
  * exported so that the reference can be linked against it (oracle/wm_subst.cpp). Returns the score. */
 int wm_ksw_ll_i16(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const int8_t *mat5x5, int gapo, int gape, int *qe, int *te);
+/* ksw_ll_qinit + ksw_ll_i16 (src/ksw2.h:82-83) as a batch on the DEVICE, one wavefront per job: out[i] = {score, qe, te} exactly as wm_ksw_ll_i16 returns them —
+ * the striped machine's padding (qe may reach qlen + 6), its saturation at 32767, E opened from the main-loop H, te = the last row that reaches the score, qe = the
+ * last striped slot of that row (csrc/ksw_ll.h is the specification, csrc/ll_kernel.h the kernel). mat5x5 as for wm_ksw_ll_i16 (row = target code).
+ *   wm_ksw_ll_batch      operands as 0..4 codes inside seqs: the query is seqs[q_off, q_off + qlen), the target seqs[t_off, t_off + tlen); step = 1 reads both from
+ *                        their first byte on, step = -1 both from their last byte backwards. Codes above 4 are clamped to 4.
+ *   wm_ksw_ll_batch_pos  operands as positions in what the device holds, the rule of wm_ksw_pos_t: query element i = index q_pos + i * step of the two-strand space
+ *                        of the (sub)read at qwin_off / qwin_len, target element i = base t_pos + i * step of contig rid.
+ * WM_EINVAL, naming the job where there is one, with out untouched: gapo <= 0 or gape <= 0 (with gapo = 0 the reference's lazy-F loop drops F values that tie, which the
+ * kernel's closed form does not reproduce; src/options.c:166-176 never lets the mapper have it), gapo + gape > 32767, qlen < 1 or tlen < 1, a length above
+ * WM_LL_MAX_LEN, a step other than 1 / -1, operands outside seqs / the contig / the resident reads (|q_pos| and qwin_len below 2^30), a position job without
+ * wm_index_upload or wm_reads_upload on this context. The reference has no length limit; the mapper serves longer jobs on the host. */
+#define WM_LL_MAX_LEN 16384     /* >= every preset's max_gap (5000; 2000 in splice mode) and the 16000 stage 2 raises it to: rows of the LDS class's hand-over buffer */
+typedef struct { uint32_t q_off, t_off; int32_t qlen, tlen; int8_t step, pad[3]; } wm_ll_job_t;
+typedef struct { int64_t qwin_off; int32_t qwin_len, q_pos, rid, t_pos, qlen, tlen; int8_t step, pad[7]; } wm_ll_pos_t;
+typedef struct { int32_t score, qe, te; } wm_ll_res_t;
+int wm_ksw_ll_batch(wm_ctx_t *ctx, const int8_t *mat5x5, int gapo, int gape, int n_jobs, const wm_ll_job_t *jobs, const uint8_t *seqs, size_t seqs_bytes, wm_ll_res_t *out);
+int wm_ksw_ll_batch_pos(wm_ctx_t *ctx, const int8_t *mat5x5, int gapo, int gape, int n_jobs, const wm_ll_pos_t *jobs, wm_ll_res_t *out);
+/* Routing knob (process-wide; results never depend on it): a job whose padded query (qlen rounded up to a multiple of 8) has at most reg_max positions keeps its
+ * whole state in registers (one pass, no LDS); every other job walks the query in passes of 64 positions that hand their last column over through LDS. 0..64,
+ * default 64 (anything else is ignored); 0 sends every job to the LDS class. wm_ksw_ll_reg_max(): the current value. Tests force either class at tiny sizes. */
+void wm_ksw_ll_set_routing(int reg_max);
+int wm_ksw_ll_reg_max(void);
+/* The mapper's switch: on = 1, the three callers of ksw_ll_i16 — the inversion test of mm_test_zdrop (src/align.c:68-89), mm_align1_inv (:797-852) and the splice end
+ * filter (mm_seed_ext_score, :523-563) — file their jobs with the batching hub, which serves all fibers' jobs with one wm_ksw_ll_batch_pos; 0 = each call runs on the
+ * host inside its fiber; < 0 = what WM_LL_DEV in the environment says (read when a mapping call starts). OFF by default. Results do not depend on it, nor on its four
+ * siblings above. */
+void wm_set_ll_device(int on);
+int wm_ll_device_enabled(void);
+/* out6: jobs deferred, served on the device, served on the host by the batched request while the switch was on (not resident, or longer than WM_LL_MAX_LEN), batched
+ * device calls, DP cells of those calls (qlen x tlen), microseconds the mapper spent inside them — process-wide since the last reset. */
+void wm_ll_stats(uint64_t *out6, int reset);
 
 /* ksw_exts2_sse as a batch (replaces src/ksw2.h:63-64, called at src/align.c:326-327 when MM_F_SPLICE is set): the splice-aware
  * extension. sc->q / e = gap open / extension, sc->q2 = the price of an intron (no extension), sc->e2 unused; noncan = the penalty of a

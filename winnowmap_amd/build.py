@@ -53,7 +53,7 @@ def _newer(target, sources):
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value", "-mllvm", "-disable-promote-alloca-to-vector"]
 
 
-UNITS = ("wm_rt", "wm_ksw", "wm_extra", "wm_eqx", "wm_cs", "wm_index", "wm_window", "wm_mapper")      # the translation units of libwmgpu.so (csrc/wm_rt.h says what each holds)
+UNITS = ("wm_rt", "wm_ksw", "wm_ll", "wm_extra", "wm_eqx", "wm_cs", "wm_index", "wm_window", "wm_mapper")      # the translation units of libwmgpu.so (csrc/wm_rt.h says what each holds)
 
 
 def build_gpu(force=False, verbose=False, out=None):
@@ -245,6 +245,20 @@ def build_emu_cs():
     return out
 
 
+def build_emu_ll():
+    """tests/simt_emu/libwm_emu_ll.so: ksw_ll_i16 on the emulator (csrc/ll_kernel.h: register class and LDS class, byte and position form), beside the
+    specification itself (csrc/ksw_ll.h) (tests/simt_emu/emu_ll.cpp)."""
+    emu = os.path.join(ROOT, "tests", "simt_emu")
+    out = os.path.join(emu, "libwm_emu_ll.so")
+    srcs = [os.path.join(emu, f) for f in ("emu_ll.cpp", "simt.h")] + \
+           [os.path.join(CSRC, f) for f in ("ll_kernel.h", "ksw_ll.h", "reads2bit.h")] + [os.path.join(ROOT, "include", "wm_gpu.h")]
+    with _Lock(out):
+        if _newer(out, srcs):
+            _run_to(out, lambda o: ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
+                                    "-I" + emu, "-I" + CSRC, "-o", o, os.path.join(emu, "emu_ll.cpp")])
+    return out
+
+
 def build_emu_fix_main(sanitize=True):
     """tests/simt_emu/emu_fix_main[_san]: emu_fix.cpp with a main of its own (emu_fix_main.cpp) that replays the cases `python tests/fixcases.py dump FILE` wrote —
     the stand-alone program for -fsanitize=address,undefined runs of the kernels' index arithmetic on the CPU."""
@@ -317,6 +331,7 @@ if __name__ == "__main__":
     build_emu_fix()
     build_emu_eqx()
     build_emu_cs()
+    build_emu_ll()
     build_emu_stripe()
     build_emu_chain()
     build_harness()

@@ -2,8 +2,10 @@
 #include "wm_align.h"
 #include "../cigar_walk.h"
 #include "../cigar_fix.h"
+#include "../ksw_ll.h"
 #include <math.h>
 #include <algorithm>
+#include <array>
 #include <list>
 #if defined(__SSE2__)
 #include <emmintrin.h>
@@ -29,10 +31,6 @@ static void gen_simple_mat(int8_t *mat, int a, int b, int sc_ambi)
 // ------------------------------------------------------------------------------------------------------------
 // ksw_ll_i16: striped local alignment score, emulated lane-exactly (8 x int16 per vector)
 // ------------------------------------------------------------------------------------------------------------
-namespace {
-inline int16_t sat_add(int a, int b) { const int s = a + b; return (int16_t)(s > 32767 ? 32767 : s < -32768 ? -32768 : s); }
-inline int16_t usub(int16_t a, int16_t b) { const uint16_t x = (uint16_t)a, y = (uint16_t)b; return (int16_t)(x > y ? x - y : 0); }
-}
 #if defined(__SSE2__)
 // the same machine on real 8 x int16 vectors (the host is x86-64 wherever the library runs today); the portable lane-by-lane form below is its
 // specification and what other hosts compile
@@ -96,61 +94,8 @@ int ll_i16_portable(int qlen, const uint8_t *query, int tlen, const uint8_t *tar
 #else
 int ll_i16(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const int8_t *mat, int gapo, int gape, int *qe, int *te)
 #endif
-{
-	const int V = 8, slen = (qlen + V - 1) / V, n = slen * V;
-	std::vector<int16_t> profile((size_t)5 * n), Hprev(n, 0), Hcur(n, 0), E(n, 0), Hbest(n, 0);
-	for (int a = 0; a < 5; ++a)
-		for (int j = 0; j < slen; ++j)
-			for (int l = 0; l < V; ++l) {
-				const int pos = j + l * slen;
-				profile[((size_t)a * slen + j) * V + l] = pos < qlen ? mat[a * 5 + query[pos]] : 0;
-			}
-	const int16_t open_ext = (int16_t)(gapo + gape), ext = (int16_t)gape;
-	int gmax = 0;
-	*qe = *te = -1;
-	for (int i = 0; i < tlen; ++i) {
-		const int16_t *S = &profile[(size_t)target[i] * n];
-		int16_t h[V], f[V], best[V];
-		h[0] = 0;
-		for (int l = 1; l < V; ++l) h[l] = Hprev[(size_t)(slen - 1) * V + l - 1];
-		for (int l = 0; l < V; ++l) f[l] = 0, best[l] = 0;
-		for (int j = 0; j < slen; ++j)
-			for (int l = 0; l < V; ++l) {
-				const size_t o = (size_t)j * V + l;
-				int16_t e = E[o], v = sat_add(h[l], S[o]);
-				v = std::max(v, e); v = std::max(v, f[l]);
-				best[l] = std::max(best[l], v);
-				Hcur[o] = v;
-				v = usub(v, open_ext);
-				E[o] = std::max(usub(e, ext), v);
-				f[l] = std::max(usub(f[l], ext), v);
-				h[l] = Hprev[o];
-			}
-		bool settled = false;
-		for (int k = 0; k < V && !settled; ++k) {              // lazy-F correction rounds
-			for (int l = V - 1; l > 0; --l) f[l] = f[l - 1];
-			f[0] = 0;
-			for (int j = 0; j < slen && !settled; ++j) {
-				bool any = false;
-				for (int l = 0; l < V; ++l) {
-					const size_t o = (size_t)j * V + l;
-					int16_t v = std::max(Hcur[o], f[l]);
-					Hcur[o] = v;
-					v = usub(v, open_ext);
-					f[l] = usub(f[l], ext);
-					any |= f[l] > v;
-				}
-				if (!any) settled = true;
-			}
-		}
-		int imax = best[0];
-		for (int l = 1; l < V; ++l) imax = std::max<int>(imax, best[l]);
-		if (imax >= gmax) { gmax = imax; *te = i; Hbest = Hcur; }
-		Hprev.swap(Hcur);
-	}
-	for (int i = 0; i < n; ++i)
-		if ((int)(uint16_t)Hbest[i] == gmax) *qe = i / V + i % V * slen;
-	return gmax;
+{   // the lane-by-lane form: one text for the host, the wavefront emulator and the tests (csrc/ksw_ll.h)
+	return wm_ksw_ll_spec(qlen, query, tlen, target, mat, gapo, gape, qe, te);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -162,6 +107,7 @@ struct AlnEnv {
 	bool q_has_n;
 	bool defer_fix = false;     // ... and their mm_fix_cigar with them (Scheduler::fix_deferred)
 	bool defer_extra = false;   // the regions' final scans wait for one batched request per read (Scheduler::extra_deferred)
+	bool defer_ll = false;      // the callers of ksw_ll_i16 file local-score requests instead of running it in the fiber (Scheduler::ll_deferred)
 	int eqx = 0;                // MM_F_EQX: 1 = mm_update_cigar_eqx runs right after every scan (src/align.c:285), 2 = it waits for one batched request per read (Scheduler::eqx_deferred)
 };
 
@@ -315,39 +261,60 @@ static void fix_bad_ends(const Reg &r, const m128 *a, int bw, int min_match, int
 	}
 }
 
-// how many leading positions of t[0..n) and q[0..n) hold the same unambiguous base (codes < 4): eight at a time
-// mm_seed_ext_score (src/align.c:523-543): local alignment score (ksw_ll_i16) of one anchor stretched by anchor_ext_len to both sides
-static int seed_ext_score(const MapOpt &opt, const Index &mi, const int8_t *mat, int qlen, const uint8_t *const qseq0[2], const m128 &a)
+// mm_seed_ext_score (src/align.c:523-543): local alignment score (ksw_ll_i16) of one anchor stretched by anchor_ext_len to both sides. The stretch itself ...
+struct SeedExt { int rid, rev, rs, re, qs, qe; };
+static SeedExt seed_ext_range(const MapOpt &opt, const Index &mi, int qlen, const m128 &a)
 {
 	const int q_span = (int)(a.y >> 32 & 0xff), ext_len = opt.anchor_ext_len;
-	const int rid = (int)(a.x << 1 >> 33);
-	int re = (int32_t)a.x + 1, rs = re - q_span, qe = (int32_t)a.y + 1, qs = qe - q_span;
-	rs = rs - ext_len > 0 ? rs - ext_len : 0;
-	qs = qs - ext_len > 0 ? qs - ext_len : 0;
-	re = re + ext_len < (int32_t)mi.seq[rid].len ? re + ext_len : (int32_t)mi.seq[rid].len;
-	qe = qe + ext_len < qlen ? qe + ext_len : qlen;
-	std::vector<uint8_t> tseq(re - rs);
-	mi.getseq(rid, rs, re, tseq.data());
+	SeedExt x;
+	x.rid = (int)(a.x << 1 >> 33); x.rev = (int)(a.x >> 63);
+	x.re = (int32_t)a.x + 1, x.rs = x.re - q_span, x.qe = (int32_t)a.y + 1, x.qs = x.qe - q_span;
+	x.rs = x.rs - ext_len > 0 ? x.rs - ext_len : 0;
+	x.qs = x.qs - ext_len > 0 ? x.qs - ext_len : 0;
+	x.re = x.re + ext_len < (int32_t)mi.seq[x.rid].len ? x.re + ext_len : (int32_t)mi.seq[x.rid].len;
+	x.qe = x.qe + ext_len < qlen ? x.qe + ext_len : qlen;
+	return x;
+}
+// ... and its score on the host
+static int seed_ext_score(const MapOpt &opt, const Index &mi, const int8_t *mat, int qlen, const uint8_t *const qseq0[2], const m128 &a)
+{
+	const SeedExt x = seed_ext_range(opt, mi, qlen, a);
+	std::vector<uint8_t> tseq(x.re - x.rs);
+	mi.getseq(x.rid, x.rs, x.re, tseq.data());
 	int q_off, t_off;
-	return ll_i16(qe - qs, qseq0[a.x >> 63] + qs, re - rs, tseq.data(), mat, opt.q, opt.e, &q_off, &t_off);
+	return ll_i16(x.qe - x.qs, qseq0[x.rev] + x.qs, x.re - x.rs, tseq.data(), mat, opt.q, opt.e, &q_off, &t_off);
 }
 
 // mm_fix_bad_ends_splice (src/align.c:545-563): a boundary anchor that sits across a long gap must carry its own weight — its span, or
-// the score of the sequence around it, has to exceed log(gap) + anchor_ext_shift; otherwise it is a tiny terminal exon placed by chance
-static void fix_bad_ends_splice(const MapOpt &opt, const Index &mi, const Reg &r, const int8_t *mat, int qlen, const uint8_t *const qseq0[2], const m128 *a, int32_t *as1, int32_t *cnt1)
+// the score of the sequence around it, has to exceed log(gap) + anchor_ext_shift; otherwise it is a tiny terminal exon placed by chance.
+// In two halves, so that the scores can come from a batched request: which of the two ends (0 = first anchor, 1 = last) need a score at all ...
+static void splice_ends_need(const MapOpt &opt, const Reg &r, const m128 *a, bool need[2])
+{
+	need[0] = need[1] = false;
+	if (r.cnt < 3) return;
+	double log_gap = std::log((double)((int32_t)a[r.as + 1].x - (int32_t)a[r.as].x));
+	need[0] = (double)(int)(a[r.as].y >> 32 & 0xff) < log_gap + opt.anchor_ext_shift;
+	log_gap = std::log((double)((int32_t)a[r.as + r.cnt - 1].x - (int32_t)a[r.as + r.cnt - 2].x));
+	need[1] = (double)(int)(a[r.as + r.cnt - 1].y >> 32 & 0xff) < log_gap + opt.anchor_ext_shift;
+}
+// ... and what the scores decide
+static void splice_ends_apply(const MapOpt &opt, const Reg &r, const int8_t *mat, const m128 *a, const bool need[2], const int score[2], int32_t *as1, int32_t *cnt1)
 {
 	*as1 = r.as, *cnt1 = r.cnt;
 	if (r.cnt < 3) return;
 	double log_gap = std::log((double)((int32_t)a[r.as + 1].x - (int32_t)a[r.as].x));
-	if ((double)(int)(a[r.as].y >> 32 & 0xff) < log_gap + opt.anchor_ext_shift) {
-		const int score = seed_ext_score(opt, mi, mat, qlen, qseq0, a[r.as]);
-		if ((double)score / mat[0] < log_gap + opt.anchor_ext_shift) ++(*as1), --(*cnt1);
-	}
+	if (need[0] && (double)score[0] / mat[0] < log_gap + opt.anchor_ext_shift) ++(*as1), --(*cnt1);
 	log_gap = std::log((double)((int32_t)a[r.as + r.cnt - 1].x - (int32_t)a[r.as + r.cnt - 2].x));
-	if ((double)(int)(a[r.as + r.cnt - 1].y >> 32 & 0xff) < log_gap + opt.anchor_ext_shift) {
-		const int score = seed_ext_score(opt, mi, mat, qlen, qseq0, a[r.as + r.cnt - 1]);
-		if ((double)score / mat[0] < log_gap + opt.anchor_ext_shift) --(*cnt1);
-	}
+	if (need[1] && (double)score[1] / mat[0] < log_gap + opt.anchor_ext_shift) --(*cnt1);
+}
+static void fix_bad_ends_splice(const MapOpt &opt, const Index &mi, const Reg &r, const int8_t *mat, int qlen, const uint8_t *const qseq0[2], const m128 *a, int32_t *as1, int32_t *cnt1)
+{
+	bool need[2];
+	int score[2] = { 0, 0 };
+	splice_ends_need(opt, r, a, need);
+	if (need[0]) score[0] = seed_ext_score(opt, mi, mat, qlen, qseq0, a[r.as]);
+	if (need[1]) score[1] = seed_ext_score(opt, mi, mat, qlen, qseq0, a[r.as + r.cnt - 1]);
+	splice_ends_apply(opt, r, mat, a, need, score, as1, cnt1);
 }
 
 static void append_cigar(Reg &r, const std::vector<uint32_t> &c)
@@ -361,17 +328,24 @@ static void append_cigar(Reg &r, const std::vector<uint32_t> &c)
 
 static bool zdwalk_on_host() { static const bool h = getenv("WM_ZDWALK_HOST") != 0; return h; }      // A/B switch: the host walks the fills' CIGARs as before
 
+// the inversion test applies (src/align.c:72): not in splice / short-read / single-strand mode, the drop exceeds zdrop_inv, and both stretches are shorter than max_gap
+static bool inv_candidate(const MapOpt &opt, const wm_zd_t &z)
+{
+	return !(opt.flag & (F_SPLICE | F_SR | F_FOR_ONLY | F_REV_ONLY)) && z.max_zdrop > opt.zdrop_inv && z.q1 - z.q0 < opt.max_gap && z.t1 - z.t0 < opt.max_gap;
+}
+// ... and its local score passes (:84-86)
+static bool inv_passes(const MapOpt &opt, int sc) { return sc >= opt.min_chain_score * opt.a && sc >= opt.min_dp_max; }
 // the verdict of mm_test_zdrop (src/align.c:68-89) given the scan's result (wm_zdrop_walk, cigar_walk.h — run by the device over the CIGAR pool of the
 // ksw call, or here): 2 = a candidate inversion (the local alignment of the reverse-complemented query stretch scores high enough), 1 = z-drop
 static int zdrop_verdict(const MapOpt &opt, const uint8_t *qseq, const uint8_t *tseq, const int8_t *mat, const wm_zd_t &z)
 {
 	const int q_len = z.q1 - z.q0, t_len = z.t1 - z.t0;
-	if (!(opt.flag & (F_SPLICE | F_SR | F_FOR_ONLY | F_REV_ONLY)) && z.max_zdrop > opt.zdrop_inv && q_len < opt.max_gap && t_len < opt.max_gap) {
+	if (inv_candidate(opt, z)) {
 		std::vector<uint8_t> q2(q_len > 0 ? q_len : 0);
 		for (int x = 0; x < q_len; ++x) { const int c = qseq[z.q1 - x - 1]; q2[x] = c >= 4 ? 4 : 3 - c; }
 		int q_off, t_off;
 		const int sc = ll_i16(q_len, q2.data(), t_len, tseq + z.t0, mat, opt.q, opt.e, &q_off, &t_off);
-		if (sc >= opt.min_chain_score * opt.a && sc >= opt.min_dp_max) return 2;
+		if (inv_passes(opt, sc)) return 2;
 	}
 	return z.max_zdrop > opt.zdrop ? 1 : 0;
 }
@@ -508,7 +482,8 @@ static void update_extra(Reg &r, const uint8_t *qseq, const uint8_t *tseq, const
 // ------------------------------------------------------------------------------------------------------------
 // one region = one mm_align1 call, split into plan → (batched ksw) → judge → (batched re-dos) → finish
 // ------------------------------------------------------------------------------------------------------------
-struct Fill { int idx; int32_t qs, qe, rs, re; int bw1; int job; int redo_job; };
+// (has_z / z / inv_job: with local-score requests deferred (AlnEnv::defer_ll), the scan of the fill's CIGAR and where its inversion test waits in the read's request list)
+struct Fill { int idx; int32_t qs, qe, rs, re; int bw1; int job; int redo_job; bool has_z = false; wm_zd_t z = { 0, -1, -1, -1, -1 }; int inv_job = -1; };
 
 struct RegAln {
 	Reg r, r2;
@@ -519,6 +494,7 @@ struct RegAln {
 	std::vector<Fill> fills;
 	std::vector<int> redo_code;
 	bool empty = false;
+	bool ends_known = false;         // as1 / cnt1 hold mm_fix_bad_ends_splice's answer already (its scores came from a batched request: align_skeleton)
 	std::vector<uint8_t> tbuf;       // reference codes of [rs0, re0): every DP of the region and the final statistics read from here
 	ExtraPend xp;                    // the region's deferred final scan (reads tbuf: align_skeleton keeps it alive)
 	bool t_has_n = false;
@@ -546,7 +522,7 @@ static void plan_reg(const AlnEnv &E, RegAln &A, m128 *a, std::vector<KswReq> &j
 	A.bw = (int)(opt.bw * 1.5 + 1.);
 	const bool is_splice = (opt.flag & F_SPLICE) != 0;
 	if (!(opt.flag & F_NO_END_FLT)) {
-		if (is_splice) fix_bad_ends_splice(opt, mi, r, E.mat, qlen, E.qseq0, a, &A.as1, &A.cnt1);
+		if (is_splice) { if (!A.ends_known) fix_bad_ends_splice(opt, mi, r, E.mat, qlen, E.qseq0, a, &A.as1, &A.cnt1); }
 		else fix_bad_ends(r, a, opt.bw, opt.min_chain_score * 2, &A.as1, &A.cnt1);
 	} else A.as1 = r.as, A.cnt1 = r.cnt;
 	int extra_flag = 0;
@@ -657,8 +633,36 @@ static void plan_reg(const AlnEnv &E, RegAln &A, m128 *a, std::vector<KswReq> &j
 	}
 }
 
+// a local-score request on operands the read already has: query element i = two-strand index q_pos + i * step of the read, target element i = tp[i * step]
+static KswReq local_job(const AlnEnv &E, int32_t q_pos, int32_t ql, int32_t rid, int32_t t_pos, const uint8_t *tp, int32_t tl, int step)
+{
+	KswReq j;
+	j.local = true;
+	j.qp = E.qseq0[0] + q_pos; j.tp = tp; j.ql = ql; j.tl = tl; j.step = step;      // (the two strands are one buffer: align_skeleton)
+	j.qwin_off = E.q_dev_off; j.qwin_len = E.qlen; j.q_pos = q_pos; j.rid = rid; j.t_pos = t_pos;
+	return j;
+}
+
+// with local-score requests deferred: the scans of a region's fills, and the inversion tests they ask for (src/align.c:72-83) appended to `inv` — the reverse
+// complement of the fill's query stretch [q0, q1) is the same stretch of the other strand, read forward: two-strand index 2L - 1 - p for p
+static void collect_inv(const AlnEnv &E, RegAln &A, const std::vector<KswReq> &jobs, std::vector<KswReq> &inv)
+{
+	if (A.empty) return;
+	for (Fill &f : A.fills) {
+		const KswReq &j = jobs[f.job];
+		if (j.has_zd) f.z = j.zd;
+		else wm_zdrop_walk(j.qp, j.tp, j.cigar.data(), (int)j.cigar.size(), E.mat[0], E.mat[1], E.mat[24], E.opt->q, E.opt->e, &f.z);
+		f.has_z = true;
+		const int q_len = f.z.q1 - f.z.q0, t_len = f.z.t1 - f.z.t0;
+		if (!inv_candidate(*E.opt, f.z) || q_len < 1 || t_len < 1) continue;          // (an empty stretch: the host form's answer, in judge_reg)
+		const int32_t q_pos = (int32_t)(j.qp - E.qseq0[0]);
+		f.inv_job = (int)inv.size();
+		inv.push_back(local_job(E, 2 * E.qlen - q_pos - f.z.q1, q_len, j.rid, j.t_pos + f.z.t0, j.tp + f.z.t0, t_len, 1));
+	}
+}
+
 // after the first pass: which fills need the exact second pass (src/align.c:736-737)
-static void judge_reg(const AlnEnv &E, RegAln &A, const std::vector<KswReq> &jobs, std::vector<KswReq> &redo)
+static void judge_reg(const AlnEnv &E, RegAln &A, const std::vector<KswReq> &jobs, std::vector<KswReq> &redo, const std::vector<KswReq> &inv)
 {
 	WM_PROF("align.judge_reg");
 	if (A.empty) return;
@@ -667,7 +671,10 @@ static void judge_reg(const AlnEnv &E, RegAln &A, const std::vector<KswReq> &job
 		Fill &f = A.fills[k];
 		const KswReq &j = jobs[f.job];
 		// (fills are never reversed) the scan comes back with the alignment when the device ran it (ksw_zdwalk_kernel), else the host walks the CIGAR
-		const int code = j.has_zd ? zdrop_verdict(*E.opt, j.qp, j.tp, E.mat, j.zd) : test_zdrop(*E.opt, j.qp, j.tp, j.cigar, E.mat);
+		int code;
+		if (f.inv_job >= 0) code = inv_passes(*E.opt, inv[f.inv_job].ez.max) ? 2 : f.z.max_zdrop > E.opt->zdrop ? 1 : 0;      // (the inversion test came back from the batched request)
+		else if (f.has_z) code = zdrop_verdict(*E.opt, j.qp, j.tp, E.mat, f.z);
+		else code = j.has_zd ? zdrop_verdict(*E.opt, j.qp, j.tp, E.mat, j.zd) : test_zdrop(*E.opt, j.qp, j.tp, j.cigar, E.mat);
 		A.redo_code[k] = code;
 		if (code != 0) {
 			KswReq d = j;                                                      // same operands, exact maximum this time
@@ -764,10 +771,18 @@ static bool align_inv(Scheduler &sch, const AlnEnv &E, const Reg &r1, const Reg 
 	if (tl < opt.min_chain_score || tl > opt.max_gap) return false;
 	std::vector<uint8_t> tseq = ref_codes(*E.idx, r1.rid, r1.re, r2.rs);
 	const uint8_t *qsrc = r1.rev ? &E.qseq0[0][r2.qe] : &E.qseq0[1][E.qlen - r2.qs];
-	std::vector<uint8_t> qr(ql), tr(tseq.rend() - tl, tseq.rend());      // (tseq carries padding behind its tl bases)
-	for (int i = 0; i < ql; ++i) qr[i] = qsrc[ql - 1 - i];
-	int q_off, t_off;
-	const int score = ll_i16(ql, qr.data(), tl, tr.data(), E.mat, opt.q, opt.e, &q_off, &t_off);
+	std::vector<uint8_t> qr, tr;
+	if (!E.defer_ll || ql < 1 || tl < 1) {
+		qr.resize(ql); tr.assign(tseq.rend() - tl, tseq.rend());           // (tseq carries padding behind its tl bases)
+		for (int i = 0; i < ql; ++i) qr[i] = qsrc[ql - 1 - i];
+	}
+	int q_off, t_off, score;
+	if (E.defer_ll && ql >= 1 && tl >= 1) {          // both operands back to front, as positions: one request, served with the other fibers'
+		std::vector<KswReq> lj(1, local_job(E, (int32_t)(qsrc - E.qseq0[0]) + ql - 1, ql, r1.rid, r2.rs - 1, tseq.data() + tl - 1, tl, -1));
+		++ll_stats().deferred;
+		sch.ksw(lj);
+		score = lj[0].ez.max; q_off = lj[0].ez.max_q; t_off = lj[0].ez.max_t;
+	} else score = ll_i16(ql, qr.data(), tl, tr.data(), E.mat, opt.q, opt.e, &q_off, &t_off);
 	if (score < opt.min_dp_max) return false;
 	// NB: the striped layout pads the query to a multiple of 8, so the best cell may sit on a pad slot and q_off can
 	// be as low as -7: the reference then starts the extension a few bases BEFORE the gap (pointer arithmetic on its
@@ -802,6 +817,7 @@ void align_skeleton(Scheduler &sch, const MapOpt &opt, const Index &idx, int qle
 	E.defer_fix = sch.fix_deferred();
 	E.defer_extra = E.defer_fix || sch.extra_deferred();
 	E.eqx = (opt.flag & F_EQX) ? (sch.eqx_deferred() ? 2 : 1) : 0;
+	E.defer_ll = sch.ll_deferred();
 	// both strands in ONE buffer, reverse complement right behind the forward strand, exactly like the reference's
 	// qseq0 (src/align.c:871-877): mm_align1_inv may step a few bases in front of a strand (see align_inv)
 	// (three flat loops the compiler vectorises — a copy, a reversed complement, an OR-reduction — instead of one byte loop with two branches:
@@ -855,7 +871,37 @@ void align_skeleton(Scheduler &sch, const MapOpt &opt, const Index &idx, int qle
 		// scoring pass is kept (src/align.c:884-900); the two passes are independent and run in the same batches
 		const bool is_splice = (opt.flag & F_SPLICE) != 0, two_strands = is_splice && (opt.flag & F_SPLICE_FOR) && (opt.flag & F_SPLICE_REV);
 		std::vector<RegAln> A(todo.size()), B(two_strands ? todo.size() : 0);
-		std::vector<KswReq> jobs, redo;
+		std::vector<KswReq> jobs, redo, inv;
+		if (E.defer_ll && is_splice && !(opt.flag & F_NO_END_FLT)) {      // mm_fix_bad_ends_splice: both ends of all these regions in one request list, before the alignment jobs are made
+			struct End { size_t k; int e; };
+			std::vector<End> ends;
+			std::vector<KswReq> lj;
+			std::list<std::vector<uint8_t>> tseqs;                      // the host views of the requests' targets
+			std::vector<std::array<bool, 2>> need(todo.size());
+			for (size_t k = 0; k < todo.size(); ++k) {
+				const Reg &r = todo[k]->r;
+				if (r.cnt == 0) continue;
+				splice_ends_need(opt, r, a, need[k].data());
+				for (int e = 0; e < 2; ++e) {
+					if (!need[k][e]) continue;
+					const SeedExt x = seed_ext_range(opt, idx, qlen, a[e ? r.as + r.cnt - 1 : r.as]);
+					tseqs.emplace_back((size_t)(x.re - x.rs));
+					idx.getseq(x.rid, x.rs, x.re, tseqs.back().data());
+					ends.push_back(End{ k, e });
+					lj.push_back(local_job(E, (x.rev ? qlen : 0) + x.qs, x.qe - x.qs, x.rid, x.rs, tseqs.back().data(), x.re - x.rs, 1));
+				}
+			}
+			ll_stats().deferred += lj.size();
+			sch.ksw(lj);
+			std::vector<std::array<int, 2>> score(todo.size(), std::array<int, 2>{ { 0, 0 } });
+			for (size_t i = 0; i < ends.size(); ++i) score[ends[i].k][ends[i].e] = lj[i].ez.max;
+			for (size_t k = 0; k < todo.size(); ++k) {
+				if (todo[k]->r.cnt == 0) continue;
+				splice_ends_apply(opt, todo[k]->r, E.mat, a, need[k].data(), score[k].data(), &A[k].as1, &A[k].cnt1);
+				A[k].ends_known = true;
+				if (two_strands) { B[k].as1 = A[k].as1; B[k].cnt1 = A[k].cnt1; B[k].ends_known = true; }
+			}
+		}
 		for (size_t k = 0; k < todo.size(); ++k) {
 			if (two_strands) { B[k].r = todo[k]->r; B[k].n_a = n_a; }
 			A[k].r = std::move(todo[k]->r); A[k].n_a = n_a;
@@ -864,7 +910,12 @@ void align_skeleton(Scheduler &sch, const MapOpt &opt, const Index &idx, int qle
 			if (two_strands) plan_reg(E, B[k], a, jobs, F_SPLICE_REV);
 		}
 		sch.ksw(jobs);
-		for (size_t k = 0; k < todo.size(); ++k) { judge_reg(E, A[k], jobs, redo); if (two_strands) judge_reg(E, B[k], jobs, redo); }
+		if (E.defer_ll) {                  // the candidate-inversion tests of all fills of these regions: one request list
+			for (size_t k = 0; k < todo.size(); ++k) { collect_inv(E, A[k], jobs, inv); if (two_strands) collect_inv(E, B[k], jobs, inv); }
+			ll_stats().deferred += inv.size();
+			sch.ksw(inv);
+		}
+		for (size_t k = 0; k < todo.size(); ++k) { judge_reg(E, A[k], jobs, redo, inv); if (two_strands) judge_reg(E, B[k], jobs, redo, inv); }
 		sch.ksw(redo);
 		for (size_t k = 0; k < todo.size(); ++k) {
 			finish_reg(E, A[k], a, jobs, redo);

@@ -132,6 +132,7 @@ struct Hub {
 	bool fix_dev = false;                   // ... and mm_fix_cigar with them, to DeviceOps::fix_extra_batch (fix_device_on() when the call started)
 	bool eqx_dev = false;                   // ... and, under MM_F_EQX, the = / X rewriting after them, to DeviceOps::eqx_batch (eqx_device_on() when the call started)
 	bool cs_dev = false;                    // ... and, under MM_F_OUT_CS / MM_F_OUT_MD, the tags' bodies of a finished read to DeviceOps::cs_batch (cs_device_on() when the call started)
+	bool ll_dev = false;                    // the callers of ksw_ll_i16 file local-score requests (KswReq::local) in the alignment queue (ll_device_on() when the call started)
 	bool extra_dev = false;                 // the mapping call defers its regions' final scans to DeviceOps::extra_batch (extra_device_on() when the call started)
 	std::vector<Fiber*> waiters[OP_N];
 	int inflight = 0, inflight_op[OP_N] = {};
@@ -312,6 +313,7 @@ public:
 		int ops = 0;
 		const long hu = hub_->heavy_units, xu = hub_->huge_units;
 		for (KswReq &r : rs) {
+			if (r.local) { l_q_[OP_KSW].push_back(&r); ops |= 1 << OP_KSW; continue; }      // a local score: no band to classify by, and --cap-sw-mat does not apply (src/align.c:78, :539, :824)
 			if (hub_->max_sw_mat > 0 && (int64_t)r.tlen() * r.qlen() > hub_->max_sw_mat) {      // --cap-sw-mat (src/align.c:323-325): not aligned, reported as z-dropped
 				r.ez = wm_ksw_result_t(); r.ez.max_q = r.ez.max_t = r.ez.mqe_t = r.ez.mte_q = -1; r.ez.score = r.ez.mqe = r.ez.mte = -0x40000000; r.ez.zdropped = 1;
 				r.cigar.clear();
@@ -324,6 +326,8 @@ public:
 		}
 		if (ops) wait(ops);
 	}
+	// the callers of ksw_ll_i16 file their jobs as local-score requests through ksw() instead of running them inside the fiber
+	bool ll_deferred() const { return hub_->ll_dev; }
 	// the deferred final scans of one read's regions (ExtraReq): one batched request, served together with those of the other reads in flight
 	bool extra_deferred() const { return hub_->extra_dev; }
 	void extra(std::vector<ExtraReq> &rs)
@@ -457,6 +461,17 @@ private:
 			case OP_CHAIN: { auto c = typed<ChainReq>(q); H.ops->chain_batch(c); break; }
 			case OP_KSW: case OP_KSW_HEAVY: case OP_KSW_HUGE: {
 				auto d = typed<KswReq>(q);
+				std::vector<KswReq*> loc;                   // the local-score requests among them (only with the switch of wm_set_ll_device on) go to their own call
+				if (H.ll_dev) for (KswReq *r : d) if (r->local) loc.push_back(r);      // (switch off: nobody files one, and the queue is not walked)
+				if (!loc.empty()) {
+					size_t k = 0;
+					for (KswReq *r : d) if (!r->local) d[k++] = r;
+					d.resize(k);
+					int8_t mat[25];                             // ksw_gen_simple_mat (src/align.c:9-22) of the call's scores
+					for (int i = 0; i < 25; ++i) mat[i] = (i / 5 == 4 || i % 5 == 4) ? H.sc.sc_ambi : i / 5 == i % 5 ? H.sc.match : H.sc.mismatch;
+					H.ops->ll_batch(mat, H.sc.q, H.sc.e, loc);
+					if (d.empty()) break;
+				}
 				if (H.splice) H.ops->exts2_batch(H.sc, H.noncan, H.junc_bonus, d);
 				else H.ops->ksw_batch(H.sc, d);
 				break;

@@ -270,6 +270,7 @@ void map_batch(const Index &idx, const MapOpt &opt, DeviceOps *ops, const std::v
 	hub.extra_dev = extra_device_on();          // (read when the mapping call starts: wm_set_extra_device / WM_EXTRA_DEV)
 	hub.fix_dev = fix_device_on();              // (... wm_set_fix_device / WM_FIX_DEV)
 	hub.cs_dev = cs_device_on();                // (... wm_set_cs_device / WM_CS_DEV; it only matters under MM_F_OUT_CS / MM_F_OUT_MD)
+	hub.ll_dev = ll_device_on();                // (... wm_set_ll_device / WM_LL_DEV)
 	hub.eqx_dev = eqx_device_on();              // (... wm_set_eqx_device / WM_EQX_DEV; it only matters under MM_F_EQX)
 	hub.n_workers = T;
 	hub.max_sw_mat = opt.max_sw_mat;

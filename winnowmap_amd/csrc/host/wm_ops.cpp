@@ -6,6 +6,7 @@
 #include "../cigar_eqx.h"
 #include "../cigar_cs.h"
 #include "wm_index.h"
+#include "wm_align.h"
 
 namespace wm {
 
@@ -151,7 +152,29 @@ void DeviceOps::cs_batch(std::vector<CsReq*> &reqs)
 	cs_stats().on_host += reqs.size();
 }
 
-// ---- the accounts of the four switches: the C entry points' copy-out, and the lines at unload --------------------------------------------------------
+// ---- ksw_ll_i16 as a batched operation: requests that travel through the alignment queue (KswReq::local) -------------------------------------------------
+static DevSwitch g_ll_dev{"WM_LL_DEV"};
+bool ll_device_on() { return g_ll_dev.on(); }
+LlStats &ll_stats() { static LlStats s; return s; }
+
+void DeviceOps::ll_batch(const int8_t *mat5x5, int gapo, int gape, std::vector<KswReq*> &reqs)
+{
+	WM_SITE("ll.host");
+	parallel_for(1, reqs.size(), [&](size_t i) {
+		KswReq &r = *reqs[i];
+		int qe = -1, te = -1;
+		if (r.step == 1) r.ez.max = ll_i16(r.ql, r.qp, r.tl, r.tp, mat5x5, gapo, gape, &qe, &te);
+		else {
+			std::vector<uint8_t> q(r.ql > 0 ? r.ql : 1), t(r.tl > 0 ? r.tl : 1);
+			r.copy_query(q.data()); r.copy_target(t.data());
+			r.ez.max = ll_i16(r.ql, q.data(), r.tl, t.data(), mat5x5, gapo, gape, &qe, &te);
+		}
+		r.ez.max_q = qe; r.ez.max_t = te;
+	});
+	ll_stats().on_host += reqs.size();
+}
+
+// ---- the accounts of the five switches: the C entry points' copy-out, and the lines at unload --------------------------------------------------------
 typedef std::initializer_list<std::atomic<uint64_t>*> StatFields;      // an account's counters in the order its entry point documents (include/wm_gpu.h)
 static void take_stats(StatFields f, uint64_t *out, int reset)
 {
@@ -172,7 +195,9 @@ static struct AccountReport {
 	~AccountReport()
 	{
 		if (!getenv("WM_EXTRA_REPORT")) return;
-		CsStats &c = cs_stats(); FixStats &f = fix_stats(); EqxStats &q = eqx_stats(); ExtraStats &x = extra_stats();
+		CsStats &c = cs_stats(); FixStats &f = fix_stats(); EqxStats &q = eqx_stats(); ExtraStats &x = extra_stats(); LlStats &l = ll_stats();
+		report_line("[wm] ll: # jobs deferred, # served on the device, # on the host, # batched calls, # cells, # us inside the calls\n",
+		            { &l.deferred, &l.on_device, &l.on_host, &l.calls, &l.cells, &l.us });
 		report_line("[wm] cs: # regions deferred, # served on the device, # on the host, # batched calls, # bytes, # us inside the calls\n",
 		            { &c.deferred, &c.on_device, &c.on_host, &c.calls, &c.bytes, &c.us });
 		report_line("[wm] fix: # regions deferred, # fixed on the device, # on the host, # early on the host (inversion test), # batched calls, # us inside the calls, # columns\n",
@@ -196,6 +221,9 @@ void wm_cs_stats(uint64_t *out6, int reset) { wm::CsStats &s = wm::cs_stats(); w
 void wm_set_eqx_device(int on) { wm::g_eqx_dev.set(on); }
 int wm_eqx_device_enabled(void) { return wm::eqx_device_on() ? 1 : 0; }
 void wm_eqx_stats(uint64_t *out6, int reset) { wm::EqxStats &s = wm::eqx_stats(); wm::take_stats({ &s.deferred, &s.on_device, &s.on_host, &s.calls, &s.cols, &s.us }, out6, reset); }
+void wm_set_ll_device(int on) { wm::g_ll_dev.set(on); }
+int wm_ll_device_enabled(void) { return wm::ll_device_on() ? 1 : 0; }
+void wm_ll_stats(uint64_t *out6, int reset) { wm::LlStats &s = wm::ll_stats(); wm::take_stats({ &s.deferred, &s.on_device, &s.on_host, &s.calls, &s.cells, &s.us }, out6, reset); }
 void wm_set_extra_device(int on) { wm::g_extra_dev.set(on); }
 int wm_extra_device_enabled(void) { return wm::extra_device_on() ? 1 : 0; }
 void wm_extra_stats(uint64_t *out6, int reset) { wm::ExtraStats &s = wm::extra_stats(); wm::take_stats({ &s.deferred, &s.on_device, &s.on_host, &s.calls, &s.cols, &s.us }, out6, reset); }

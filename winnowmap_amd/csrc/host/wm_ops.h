@@ -77,6 +77,10 @@ struct KswReq {                    // ksw_extd2_sse (src/ksw2.h:60)
 	// alignment (has_zd + zd, see cigar_walk.h); without it the host walks the CIGAR itself
 	bool want_zd = false, has_zd = false;
 	wm_zd_t zd = { 0, -1, -1, -1, -1 };
+	// local: not an extension but ksw_ll_qinit + ksw_ll_i16 (src/ksw2.h:82-83) on the same operands — the inversion test, mm_align1_inv's placement, the splice end
+	// filter, filed while the switch of wm_set_ll_device is on. w, zdrop, end_bonus and flag are ignored; ez.max = the score, ez.max_q = qe, ez.max_t = te (the
+	// striped machine's, csrc/ksw_ll.h); there is no CIGAR. The hub hands such requests to DeviceOps::ll_batch: ksw_batch / exts2_batch never see one.
+	bool local = false;
 	wm_ksw_result_t ez = {};       // out
 	std::vector<uint32_t> cigar;   // out
 	int qlen() const { return ql; }
@@ -177,6 +181,12 @@ bool cs_device_on();
 struct CsStats { std::atomic<uint64_t> deferred{0}, on_device{0}, on_host{0}, calls{0}, bytes{0}, us{0}; };
 CsStats &cs_stats();
 
+// The switch for ksw_ll_i16 (wm_set_ll_device / WM_LL_DEV; off by default) and its account (wm_ll_stats): jobs deferred, served on the device, served on the host by the
+// batched request, batched device calls, DP cells of those calls, microseconds inside them.
+bool ll_device_on();
+struct LlStats { std::atomic<uint64_t> deferred{0}, on_device{0}, on_host{0}, calls{0}, cells{0}, us{0}; };
+LlStats &ll_stats();
+
 // The batch calls are synchronous (they return when the results are in the requests) and must be callable from several threads at
 // once: the hub (wm_fiber.h) keeps up to max_inflight() of them running concurrently.
 struct DeviceOps {
@@ -197,6 +207,10 @@ struct DeviceOps {
 	// splice mode: the same requests through ksw_exts2_sse (src/align.c:326-327) — no band, no end bonus, sc.q2 = the price of an intron;
 	// KswReq::flag carries the KSW_EZ_SPLICE_* bits. No junction annotation (mm_idx_bed_junc: the BED reader is outside the path).
 	virtual void exts2_batch(const wm_ksw_score_t &sc, int noncan, int junc_bonus, std::vector<KswReq*> &reqs) = 0;
+	// the local-score requests (KswReq::local, the switch above) that the hub split off the alignment queue. The default runs the specification's host form
+	// (wm::ll_i16) on the host views — checker-backed implementations need nothing; the product's GpuOps overrides it with wm_ksw_ll_batch_pos when every request is
+	// resident and within WM_LL_MAX_LEN.
+	virtual void ll_batch(const int8_t *mat5x5, int gapo, int gape, std::vector<KswReq*> &reqs);
 	// the deferred final scans of a mapping call's regions (the switch above). The default walks them on the host (wm_extra_walk / its SSE form) — checker-backed
 	// implementations need nothing; the product's GpuOps overrides it with wm_extra_batch_pos when every request is resident.
 	virtual void extra_batch(const wm_extra_score_t &sc, std::vector<ExtraReq*> &reqs);

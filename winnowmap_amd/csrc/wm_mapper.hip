@@ -404,6 +404,29 @@ struct GpuOpsCtx {
 		st.on_device += (uint64_t)n; ++st.calls; st.bytes += (uint64_t)used; st.us += (uint64_t)((now_ms() - t0) * 1e3);
 		return true;
 	}
+	// the local-score requests (ksw_ll_qinit + ksw_ll_i16, src/ksw2.h:82-83: KswReq::local) through wm_ksw_ll_batch_pos: a handful of integers per job go out, three come
+	// back. Returns false — nothing done — unless the reads are resident and the call would not be refused (CallOps::ll_batch hands over eligible requests only).
+	bool ll_batch(const int8_t *mat, int gapo, int gape, std::vector<wm::KswReq*> &reqs)
+	{
+		const int n = (int)reqs.size();
+		if (!resident || n == 0 || gapo <= 0 || gape <= 0 || gapo + gape > 32767) return false;
+		const double t0 = now_ms();
+		std::vector<wm_ll_pos_t> jobs(n);
+		std::vector<wm_ll_res_t> res(n);
+		uint64_t cells = 0;
+		for (int i = 0; i < n; ++i) {
+			const wm::KswReq &r = *reqs[i];
+			wm_ll_pos_t &j = jobs[i];
+			memset(&j, 0, sizeof(j));
+			j.qwin_off = r.qwin_off; j.qwin_len = r.qwin_len; j.q_pos = r.q_pos; j.rid = r.rid; j.t_pos = r.t_pos; j.qlen = r.ql; j.tlen = r.tl; j.step = (int8_t)r.step;
+			cells += (uint64_t)r.ql * (uint64_t)r.tl;
+		}
+		if (wm_ksw_ll_batch_pos(c, mat, gapo, gape, n, jobs.data(), res.data())) { fail("ksw_ll"); return true; }
+		for (int i = 0; i < n; ++i) { reqs[i]->ez.max = res[i].score; reqs[i]->ez.max_q = res[i].qe; reqs[i]->ez.max_t = res[i].te; }
+		wm::LlStats &st = wm::ll_stats();
+		st.on_device += (uint64_t)n; ++st.calls; st.cells += cells; st.us += (uint64_t)((now_ms() - t0) * 1e3);
+		return true;
+	}
 	// splice mode (src/align.c:326-327): the requests through wm_ksw_exts2_batch, in groups whose unbanded traceback matrices fit the arena
 	void exts2_batch(const wm_ksw_score_t &sc, int noncan, int junc_bonus, std::vector<wm::KswReq*> &reqs)
 	{
@@ -630,6 +653,13 @@ struct CallOps : wm::DeviceOps {
 		std::vector<wm::CsReq*> rest;
 		g.batch_or_rest(err, reqs, rest, [](GpuOpsCtx &x, std::vector<wm::CsReq*> &part) { return x.cs_batch(part); });
 		if (!rest.empty()) wm::DeviceOps::cs_batch(rest);                  // not resident, or the device call would refuse it: the host specification (counted by wm_cs_stats)
+	}
+	void ll_batch(const int8_t *mat, int gapo, int gape, std::vector<wm::KswReq*> &reqs) override
+	{
+		std::vector<wm::KswReq*> dev, rest;
+		for (wm::KswReq *r : reqs) (r->resident() && r->ql >= 1 && r->tl >= 1 && r->ql <= WM_LL_MAX_LEN && r->tl <= WM_LL_MAX_LEN ? dev : rest).push_back(r);
+		if (!dev.empty()) g.batch_or_rest(err, dev, rest, [&](GpuOpsCtx &x, std::vector<wm::KswReq*> &part) { return x.ll_batch(mat, gapo, gape, part); });
+		if (!rest.empty()) wm::DeviceOps::ll_batch(mat, gapo, gape, rest);    // not resident, or longer than WM_LL_MAX_LEN: the host form (counted by wm_ll_stats)
 	}
 	void eqx_batch(std::vector<wm::EqxReq*> &reqs) override
 	{

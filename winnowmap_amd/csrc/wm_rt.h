@@ -2,6 +2,7 @@
 // 3 900-line translation unit; it is six now —
 //   wm_rt.hip      runtime: errors, device contexts, arena, pinned slab, process-wide defaults; final_stage, the staging step of the three final-CIGAR units
 //   wm_ksw.hip     the alignment kernels' entry points, routing, batch planning / launch / fetch (ksw2: src/ksw2_extd2_sse.c, src/ksw2_exts2_sse.c)
+//   wm_ll.hip      ksw_ll_i16 over batches of jobs (src/ksw2_ll_sse.c:80-147): entry points, what the call refuses, the size classes and their launches
 //   wm_extra.hip   the scan of mm_update_extra over batches of final CIGARs (src/align.c:240-286): entry points, what the pass measures and refuses, launches
 //                  ... and mm_fix_cigar in front of it (src/align.c:91-167; fix_kernel.h): wm_fix_extra_batch / wm_fix_extra_batch_pos
 //   wm_cs.hip      the bodies of the cs:Z / MD:Z tags over batches of final CIGARs (src/format.c:141-218): entry points, what the pass measures and refuses, the two passes

@@ -142,6 +142,31 @@ class Context:
         _chk(lib().wm_ksw_batch_pos_zd(self._h, C.byref(score), len(jobs), jobs.ctypes.data, res.ctypes.data, pool.ctypes.data, cap, C.byref(used), zd.ctypes.data))
         return res, pool[:used.value], zd
 
+    # ---- ksw_ll_i16: the local-alignment score with the striped machine's end coordinates -----------------
+    def ksw_ll_batch(self, mat5x5, gapo, gape, jobs, seqs, out=None):
+        """wm_ksw_ll_batch: jobs: structured array LL_JOB_DTYPE (operands as 0..4 codes inside seqs, step = 1 / -1). Returns int32 [n, 3] = score, qe, te per job,
+        exactly what wm_ksw_ll_i16 returns (in `out` if one is given: a refused call leaves it untouched)."""
+        jobs = np.ascontiguousarray(jobs, LL_JOB_DTYPE)
+        seqs = np.ascontiguousarray(seqs, np.uint8)
+        mat = np.ascontiguousarray(mat5x5, np.int8)
+        assert LL_JOB_DTYPE.itemsize == 20 and mat.shape == (25,)
+        out = np.zeros((len(jobs), 3), np.int32) if out is None else out
+        assert out.dtype == np.int32 and out.flags.c_contiguous and out.size >= 3 * len(jobs)
+        lib().wm_ksw_ll_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        _chk(lib().wm_ksw_ll_batch(self._h, mat.ctypes.data, int(gapo), int(gape), len(jobs), jobs.ctypes.data, seqs.ctypes.data, seqs.nbytes, out.ctypes.data))
+        return out
+
+    def ksw_ll_batch_pos(self, mat5x5, gapo, gape, jobs, out=None):
+        """wm_ksw_ll_batch_pos: jobs: structured array LL_POS_DTYPE (operands as positions in the resident reads, two-strand space, and the uploaded reference)"""
+        jobs = np.ascontiguousarray(jobs, LL_POS_DTYPE)
+        mat = np.ascontiguousarray(mat5x5, np.int8)
+        assert LL_POS_DTYPE.itemsize == 40 and mat.shape == (25,)
+        out = np.zeros((len(jobs), 3), np.int32) if out is None else out
+        assert out.dtype == np.int32 and out.flags.c_contiguous and out.size >= 3 * len(jobs)
+        lib().wm_ksw_ll_batch_pos.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _chk(lib().wm_ksw_ll_batch_pos(self._h, mat.ctypes.data, int(gapo), int(gape), len(jobs), jobs.ctypes.data, out.ctypes.data))
+        return out
+
     # ---- the scan of mm_update_extra over final CIGARs ----------------------------------------------
     def extra_batch(self, score, jobs, seqs, cigars):
         """wm_extra_batch: score = (match, mismatch, ambi, q, e) as literal values; jobs: structured array EXTRA_JOB_DTYPE (operands as 0..4 codes inside
@@ -443,6 +468,31 @@ set_cs_device, cs_device_enabled, cs_stats = _device_switch("cs", CS_STAT_NAMES,
     """wm_set_cs_device: under MM_F_OUT_CS / MM_F_OUT_MD the mapper has the bodies of a read's cs:Z / MD:Z tags produced by one batched wm_cs_batch_pos per read (off
     by default; on < 0: back to what WM_CS_DEV in the environment says). Read when a mapping call starts; results never depend on it.""",
     """wm_cs_stats: regions deferred / served on the device / served on the host by the batched request, batched device calls, bytes produced, microseconds""")
+
+
+LL_JOB_DTYPE = np.dtype([("q_off", np.uint32), ("t_off", np.uint32), ("qlen", np.int32), ("tlen", np.int32), ("step", np.int8), ("pad", np.int8, 3)])      # wm_ll_job_t
+LL_POS_DTYPE = np.dtype([("qwin_off", np.int64), ("qwin_len", np.int32), ("q_pos", np.int32), ("rid", np.int32), ("t_pos", np.int32), ("qlen", np.int32),
+                         ("tlen", np.int32), ("step", np.int8), ("pad", np.int8, 7)])                                                           # wm_ll_pos_t
+LL_MAX_LEN = 16384                                                                                                                          # WM_LL_MAX_LEN
+LL_STAT_NAMES = ("deferred", "on_device", "on_host", "calls", "cells", "device_us")
+
+
+def set_ksw_ll_routing(reg_max):
+    """wm_ksw_ll_set_routing: up to how many positions of the padded query a ksw_ll job keeps its state in registers, 0..64 (results never depend on it)"""
+    lib().wm_ksw_ll_set_routing.argtypes = [C.c_int]
+    lib().wm_ksw_ll_set_routing.restype = None
+    lib().wm_ksw_ll_set_routing(int(reg_max))
+
+
+def ksw_ll_reg_max():
+    lib().wm_ksw_ll_reg_max.restype = C.c_int
+    return int(lib().wm_ksw_ll_reg_max())
+
+
+set_ll_device, ll_device_enabled, ll_stats = _device_switch("ll", LL_STAT_NAMES,
+    """wm_set_ll_device: the mapper files its ksw_ll_i16 jobs (inversion test, mm_align1_inv, splice end filter) with the batching hub, which serves them with batched
+    wm_ksw_ll_batch_pos calls (off by default; on < 0: back to what WM_LL_DEV in the environment says). Read when a mapping call starts; results never depend on it.""",
+    """wm_ll_stats: jobs deferred / served on the device / served on the host by the batched request, batched device calls, DP cells, microseconds""")
 
 
 def set_ksw_routing(on=-1, rows4=-1, rows8=-1):
