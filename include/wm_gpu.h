@@ -187,7 +187,8 @@ void wm_fix_stats(uint64_t *out7, int reset);
  * and so does this call (in_place = 1); otherwise every M op is replaced by its runs, a zero-length M op vanishes, every other op is copied as it stands.
  * Jobs, operands and cigars as for wm_extra_batch[_pos] (the operands already advanced by mm_fix_cigar's shifts). Job i's new CIGAR lies at cigars_out + out[i].off
  * and has out[i].n_cigar ops; the outputs lie back to back in job order. out_cap: ops cigars_out holds. WM_ENOMEM if it is too small: *out_used then holds the
- * needed count and out[] is already filled (the rule of wm_ksw_batch's cigar_cap). n_cigar == 0 is valid and gives nothing. WM_EINVAL, naming the job, for what
+ * needed count and out[] is already filled (the rule of wm_ksw_batch's cigar_cap); WM_ENOMEM for the arena ("does not fit the arena", before or after the count pass)
+ * leaves out[] and cigars_out as they were. n_cigar == 0 is valid and gives nothing. WM_EINVAL, naming the job, for what
  * wm_extra_batch[_pos] refuses about operands and n_ops; there is no score, hence no score limit. Results do not depend on wm_extra_set_routing, whose two values
  * route this call as well (a job's columns here are its M columns). */
 typedef struct { uint64_t off; int32_t n_cigar, in_place; } wm_eqx_res_t;
@@ -211,8 +212,8 @@ void wm_eqx_stats(uint64_t *out6, int reset);
  * zero-length I / D prints the bare sign, :169-178); "~<t0><t1><len><t[len-2]><t[len-1]>" (:181). MD: one run over the whole CIGAR, through I and N ops;
  * "<run><T>" at a mismatch and "<run>^<BASES>" at a D, "0" included; the final run only if it is > 0 (:199-216). Jobs, operands and cigars as for
  * wm_eqx_batch[_pos]; ops of code 0, 7 and 8 consume both operands. Job i's body lies at text_out + out[i].off and has out[i].len bytes; the bodies lie back to
- * back in job order. out_cap: bytes text_out holds. WM_ENOMEM if it is too small: *out_used then holds the needed bytes and out[] is already filled (the rule of
- * wm_eqx_batch). n_cigar == 0 is valid and gives len 0. WM_EINVAL, naming the job: what wm_eqx_batch[_pos] refuses about operands and n_ops; an op code outside
+ * back in job order. out_cap: bytes text_out holds. WM_ENOMEM if it is too small: *out_used then holds the needed bytes and out[] is already filled, an arena refusal leaves out[]
+ * and text_out as they were (the rules of wm_eqx_batch). n_cigar == 0 is valid and gives len 0. WM_EINVAL, naming the job: what wm_eqx_batch[_pos] refuses about operands and n_ops; an op code outside
  * {0, 1, 2, 3, 7, 8} (the assert of :147 / :195); in a cs mode an N op shorter than 2 (the assert of :180); a job whose bound of output bytes (3 per M column,
  * 1 per gap base, 12 per op, 16 per N, + 11) reaches 2^31 — arithmetic inside a job is int32, offsets of jobs are 64-bit. WM_EINVAL also for a mode outside
  * 0..2. Results do not depend on wm_extra_set_routing, whose two values route this call as well: a job's columns here are its M columns, EVERY base of an I / D
@@ -468,6 +469,10 @@ void wm_sdust_stats(double *out5, int reset);
 /* process-wide account of splice mode's alignment calls since the last reset: out2 = calls of the mapper's exts2 operation that held requests, and the groups
  * those calls were split into so that each group's unbanded traceback fits 0.6 of its context's arena (one wm_ksw_exts2_batch per group) */
 void wm_exts2_stats(uint64_t *out2, int reset);
+/* process-wide account of the mapper's arena splits since the last reset: a batched call of the mapper whose buffers do not fit its context's arena (WM_ENOMEM,
+ * "does not fit the arena") is served in halves, recursively. out2 = calls, or parts of one, that were refused for the arena and halved, and the parts finally
+ * issued without being halved again (a call that fits at once counts as one part; so does a part that fails for another reason, or for the arena at one request) */
+void wm_arena_split_stats(uint64_t *out2, int reset);
 /* kernel time of the last sketch/seed/chain/window batch call (HIP events on the context stream), ms */
 float wm_last_aux_ms(const wm_ctx_t *ctx);
 /* Sequences of WM_SKETCH_LONG (65 536) codes and more are sketched in chunks of WM_SKETCH_CHUNK (16 384) positions, one wavefront per chunk, by

@@ -145,3 +145,14 @@ def test_exts2_stats_is_a_process_wide_account(lib):
     lib.wm_exts2_stats(out.ctypes.data, 0)
     assert out.tolist() == [0, 0] and gpu.exts2_stats() == {"calls": 0, "groups": 0}
     lib.wm_exts2_stats(None, 0)
+
+
+def test_arena_split_stats_is_a_process_wide_account(lib):
+    """wm_arena_split_stats (batched calls of the mapper halved for the arena, and the parts issued) answers without a device, and resets"""
+    out = np.full(2, 7, np.uint64)
+    lib.wm_arena_split_stats.argtypes = [C.c_void_p, C.c_int]
+    lib.wm_arena_split_stats.restype = None
+    lib.wm_arena_split_stats(out.ctypes.data, 1)
+    lib.wm_arena_split_stats(out.ctypes.data, 0)
+    assert out.tolist() == [0, 0] and gpu.arena_split_stats() == (0, 0)
+    lib.wm_arena_split_stats(None, 0)

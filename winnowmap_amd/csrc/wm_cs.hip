@@ -143,16 +143,18 @@ try {
 	}
 	hipLaunchKernelGGL(cs_job_scan_kernel, dim3(1), dim3(64), 0, c->stream, d_cnt, n_jobs, d_res, d_total);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(out, d_res, nj * sizeof(wm_cs_res_t), hipMemcpyDeviceToHost, c->stream));
+	std::vector<wm_cs_res_t> res(nj);                                  // (out[] stays untouched when the arena refuses the write pass: a refused batch is split and issued again)
+	HIPCHK(hipMemcpyAsync(res.data(), d_res, nj * sizeof(wm_cs_res_t), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(ctx_sync(c));
-	const uint64_t total = out[nj - 1].off + (uint64_t)out[nj - 1].len;
+	const uint64_t total = res[nj - 1].off + (uint64_t)res[nj - 1].len;
 	*out_used = (size_t)total;
 	if (total > bound_all) return set_err(WM_ENODEV, "internal: the count pass reports %llu bytes, more than the %llu the batch can have", (unsigned long long)total, (unsigned long long)bound_all);
-	if (total > out_cap) return set_err(WM_ENOMEM, "text_out holds %zu bytes, the batch needs %llu", out_cap, (unsigned long long)total);
-	if (total == 0) return WM_OK;
+	if (total > out_cap) { memcpy(out, res.data(), nj * sizeof(wm_cs_res_t)); return set_err(WM_ENOMEM, "text_out holds %zu bytes, the batch needs %llu", out_cap, (unsigned long long)total); }
+	if (total == 0) { memcpy(out, res.data(), nj * sizeof(wm_cs_res_t)); return WM_OK; }
 	// ---- write: every job walks its columns again, every lane from its own byte offset ----
 	uint8_t *d_out = (uint8_t*)arena_take(c, (size_t)total + 64);
 	if (!d_out) return set_err(WM_ENOMEM, "cs batch (%llu bytes out) does not fit the arena of %.1f MB; split it", (unsigned long long)total, c->arena_bytes / 1048576.0);
+	memcpy(out, res.data(), nj * sizeof(wm_cs_res_t));
 	if (n_short) {
 		if (pos) hipLaunchKernelGGL(cs_short_write_kernel<true>, dim3((unsigned)n_short), dim3(64), 0, c->stream, d_jobs, V.order, D, P, mode, tile_cols, d_res, d_out);
 		else hipLaunchKernelGGL(cs_short_write_kernel<false>, dim3((unsigned)n_short), dim3(64), 0, c->stream, d_jobs, V.order, D, P, mode, tile_cols, d_res, d_out);

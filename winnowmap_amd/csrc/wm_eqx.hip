@@ -146,22 +146,24 @@ try {
 	}
 	hipLaunchKernelGGL(eqx_job_scan_kernel, dim3(1), dim3(64), 0, c->stream, d_cnt, n_jobs, d_res, d_total);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(out, d_res, nj * sizeof(wm_eqx_res_t), hipMemcpyDeviceToHost, c->stream));
+	std::vector<wm_eqx_res_t> res(nj);                                 // (out[] stays untouched when the arena refuses the write pass: a refused batch is split and issued again)
+	HIPCHK(hipMemcpyAsync(res.data(), d_res, nj * sizeof(wm_eqx_res_t), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(ctx_sync(c));
-	const size_t total = (size_t)out[nj - 1].off + (size_t)out[nj - 1].n_cigar;
+	const size_t total = (size_t)res[nj - 1].off + (size_t)res[nj - 1].n_cigar;
 	*out_used = total;
 	if (total > bound) return set_err(WM_ENODEV, "internal: the count pass reports %zu ops, more than the %llu the batch can have", total, (unsigned long long)bound);
-	if (total > out_cap) return set_err(WM_ENOMEM, "cigars_out holds %zu ops, the batch needs %zu", out_cap, total);
-	if (total == 0) return WM_OK;
+	if (total > out_cap) { memcpy(out, res.data(), nj * sizeof(wm_eqx_res_t)); return set_err(WM_ENOMEM, "cigars_out holds %zu ops, the batch needs %zu", out_cap, total); }
+	if (total == 0) { memcpy(out, res.data(), nj * sizeof(wm_eqx_res_t)); return WM_OK; }
 	// ---- write: the jobs of the rewrite branch walk their columns again; then every job's ops ----
 	uint32_t *d_out = (uint32_t*)arena_take(c, (total + 16) * 4);
 	std::vector<int> order2; std::vector<wm_final_pair> tmap2;
-	for (size_t g = 0; g < n_short; ++g) if (!out[order[g]].in_place && mcols[order[g]] > 0) order2.push_back(order[g]);
-	for (size_t g = 0; g < n_tiles; ++g) if (!out[tmap[g].x].in_place) tmap2.push_back(tmap[g]);
+	for (size_t g = 0; g < n_short; ++g) if (!res[order[g]].in_place && mcols[order[g]] > 0) order2.push_back(order[g]);
+	for (size_t g = 0; g < n_tiles; ++g) if (!res[tmap[g].x].in_place) tmap2.push_back(tmap[g]);
 	int *d_order2 = (int*)arena_take(c, (order2.size() + 16) * 4);
 	int2 *d_tmap2 = (int2*)arena_take(c, (tmap2.size() + 16) * sizeof(int2));
 	if (!d_out || !d_order2 || !d_tmap2)
 		return set_err(WM_ENOMEM, "eqx batch (%zu ops out) does not fit the arena of %.1f MB; split it", total, c->arena_bytes / 1048576.0);
+	memcpy(out, res.data(), nj * sizeof(wm_eqx_res_t));
 	if (!order2.empty()) {
 		HIPCHK(hipMemcpyAsync(d_order2, order2.data(), order2.size() * 4, hipMemcpyHostToDevice, c->stream));
 		if (pos) hipLaunchKernelGGL(eqx_short_write_kernel<true>, dim3((unsigned)order2.size()), dim3(64), 0, c->stream, d_jobs, d_order2, D, P, tile_cols, d_res, d_out);

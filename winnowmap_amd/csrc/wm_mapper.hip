@@ -27,6 +27,14 @@ extern "C" void wm_exts2_stats(uint64_t *out2, int reset)
 	if (out2) { out2[0] = g_exts2_calls.load(); out2[1] = g_exts2_groups.load(); }
 	if (reset) { g_exts2_calls = 0; g_exts2_groups = 0; }
 }
+// process-wide account of GpuOps::run_split (wm_arena_split_stats): batched calls (or parts of one) that were refused for the arena and halved, and the parts
+// that were finally issued without being halved again
+static std::atomic<uint64_t> g_split_halved{0}, g_split_parts{0};
+extern "C" void wm_arena_split_stats(uint64_t *out2, int reset)
+{
+	if (out2) { out2[0] = g_split_halved.load(); out2[1] = g_split_parts.load(); }
+	if (reset) { g_split_halved = 0; g_split_parts = 0; }
+}
 
 // ======================================================================================================
 // GpuOps: the product implementation of the mapper's device operations
@@ -585,8 +593,9 @@ struct GpuOps {                          // the device contexts of a mapper, sha
 	{
 		if (!x.error.empty()) return;          // an earlier part of this call failed for good: nothing more is attempted (and nothing is cleared)
 		f(reqs);
-		if (x.error.empty() || reqs.size() < 2 || x.error.find("does not fit the arena") == std::string::npos) return;
+		if (x.error.empty() || reqs.size() < 2 || x.error.find("does not fit the arena") == std::string::npos) { ++g_split_parts; return; }
 		x.error.clear();                       // (set by THIS call: the context was clean on entry)
+		++g_split_halved;
 		std::vector<R*> a(reqs.begin(), reqs.begin() + reqs.size() / 2), b(reqs.begin() + reqs.size() / 2, reqs.end());
 		run_split(x, a, f);
 		if (x.error.empty()) run_split(x, b, f);

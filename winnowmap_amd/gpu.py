@@ -559,6 +559,15 @@ def exts2_stats(reset=False):
     return {"calls": int(out[0]), "groups": int(out[1])}
 
 
+def arena_split_stats(reset=False):
+    """wm_arena_split_stats: (batched calls of the mapper, or parts of one, refused for the arena and halved; parts finally issued), process-wide since the last reset"""
+    out = np.zeros(2, np.uint64)
+    lib().wm_arena_split_stats.argtypes = [C.c_void_p, C.c_int]
+    lib().wm_arena_split_stats.restype = None
+    lib().wm_arena_split_stats(out.ctypes.data, 1 if reset else 0)
+    return int(out[0]), int(out[1])
+
+
 def build_defines():
     """the kernel-variant defines the loaded library was compiled with (wm_build_defines)"""
     lib().wm_build_defines.restype = C.c_char_p
